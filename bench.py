@@ -8,9 +8,17 @@ labelling (K=1), 400 classes, fp32. One step = forward of the 10-block stack
 backward + (N>1) RCCL gradient all-reduce + Adam update (FusedAdam: one HIP
 launch; --torch-ops for torch's head / loss / Adam). Inputs are resident in HBM before timing.
 
-Run: python bench.py [--gpus N --steps K --warmup W]
+Run: python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
      (N>1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N)
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the line (value,
+ms_per_step, loss). --dump-outputs DIR also writes what the last timed step
+returned and left behind (loss, logits, every parameter and its gradient) as
+DIR/<name>.npy. --full adds every other measurement to the line: two more timed
+windows, the other fp32 GEMM modes, the batch sweep, the clock state, per-block
+and per-kernel (roofline) timing and the CPU baseline; the --no-* options
+drop single legs of it.
 """
 import argparse
 import json
@@ -454,6 +462,33 @@ def pmc_lookup(table, sym):
     return table[hits[0]] if len(hits) == 1 else None
 
 
+DUMP_BUDGET_BYTES = 64 * 10 ** 6  # --dump-outputs: at most this much in all
+
+
+def dump_outputs(dirname, loss, logits, model):
+    """Writes the last timed step's results as <dirname>/<name>.npy (float32):
+    what the step returned (loss, logits) and what it left to its caller (every
+    parameter after the update as param.<name>, its gradient as grad.<name>).
+    Beyond DUMP_BUDGET_BYTES in all, every large array is cut to the same
+    fraction of its elements, drawn once from a fixed seed."""
+    import numpy as np
+    arrays = {"loss": loss.reshape(1), "logits": logits}
+    for name, p in model.named_parameters():
+        arrays[f"param.{name}"] = p
+        if p.grad is not None:
+            arrays[f"grad.{name}"] = p.grad
+    arrays = {k: v.detach().float().cpu().contiguous().numpy() for k, v in arrays.items()}
+    small = sum(a.nbytes + 128 for a in arrays.values() if a.size <= 4096)  # (+ .npy header)
+    large = sum(a.nbytes + 128 for a in arrays.values() if a.size > 4096)
+    keep = min(1.0, (DUMP_BUDGET_BYTES - small) / max(large, 1))
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        if keep < 1.0 and a.size > 4096:
+            idx = np.random.default_rng(0).choice(a.size, int(a.size * keep), replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(dirname, k + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -462,6 +497,14 @@ def main():
     ap.add_argument("--batch", type=int, default=CFG["N"], help="clips per GPU")
     ap.add_argument("--config", choices=sorted(CONFIGS), default="cfg2",
                     help="BASELINE.json workload (default cfg2, the headline metric)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's loss, logits, parameters and gradients "
+                         "as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps: two more timed windows, the other fp32 GEMM "
+                         "modes, the batch sweep, the GPU clock state, per-block and per-kernel "
+                         "(roofline) timing and the CPU baseline (the --no-* options below drop "
+                         "single legs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--f32-gemm", choices=["mfma", "bf16x3", "f16x2", "f16x2-nog"], default="f16x2",
@@ -532,20 +575,21 @@ def main():
         else:
             opt.zero_grad(set_to_none=True)
         if args.torch_ops:
-            loss = torch.nn.functional.cross_entropy(model.forward_nctv(x), labels)
+            logits = model.forward_nctv(x)
+            loss = torch.nn.functional.cross_entropy(logits, labels)
         else:  # fused HIP head: avg-pool + Linear + cross entropy
-            loss, _ = model.forward_loss(x, labels)
+            loss, logits = model.forward_loss(x, labels)
         loss.backward()
         if dp is not None:
             dp.synchronize()
         opt.step()
-        return loss
+        return loss, logits
 
     progress(f"{args.config}: model built, {args.warmup} warm-up steps")
     def fwd_bwd():  # (ranks > 1, graphed: dp.zero_grad / synchronize by GraphedDPStep)
-        loss, _ = model.forward_loss(x, labels)
+        loss, logits = model.forward_loss(x, labels)
         loss.backward()
-        return loss
+        return loss, logits
 
     run = step
     if graph_on:  # the W warm-up steps: a few eager (the capture needs one), the
@@ -564,7 +608,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = run()
+        loss, logits = run()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -573,6 +617,8 @@ def main():
     # the loss of the first timed window's last step (a graph's output tensor is
     # rewritten by every later replay)
     loss_first = float(loss.item())
+    if args.dump_outputs and rank == 0:  # (before any --full leg steps the model on)
+        dump_outputs(args.dump_outputs, loss, logits, model)
     if world > 1:
         t = torch.tensor([dt], device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -583,7 +629,7 @@ def main():
     # three; `value` stays the first window, timed exactly as the contract says
     runs = [clips]
     smi = None  # rocm-smi sample taken during the last repeat window (under load)
-    for rep in range(2 if args.repeats else 0):
+    for rep in range(2 if args.full and args.repeats else 0):
         if rep == 1 and rank == 0:
             smi = gpu_state_start()
         torch.cuda.synchronize()
@@ -610,7 +656,7 @@ def main():
     # v_mfma_f32_32x32x2_f32; bf16x3) timed beside the default, same model and
     # inputs (N=1 only)
     alt = None
-    if world == 1 and not cfg["bf16"] and not args.no_alt:
+    if args.full and world == 1 and not cfg["bf16"] and not args.no_alt:
         alt = []
         for mode in ("mfma", "bf16x3", "f16x2"):
             if mode == cfg["f32_gemm"]:
@@ -634,7 +680,7 @@ def main():
     # the bench batch), same model and step, 5 timed steps each after 2 warm-up
     # steps; reported as extra keys, `value` stays the bench batch
     sweep = None
-    if world == 1 and args.sweep and args.config == "cfg2":
+    if args.full and world == 1 and args.sweep and args.config == "cfg2":
         sweep = {str(cfg["N"]): round(clips, 2)}
         for nb in (32, 64, 256):
             if nb == cfg["N"]:
@@ -684,15 +730,16 @@ def main():
             "runs_clips_s": [round(r, 2) for r in runs],
             "median_clips_s": round(sorted(runs)[len(runs) // 2], 2),
             "loss": round(loss_first, 5),
-            "step_mode": "hip_graph" if graph_on else "eager",
+            "step_mode": "hip_graph" if graph_on else "eager", "full": args.full,
         }
-        out["gpu_state_under_load"] = gpu_state_read(smi)
-        out["gpu_state_after"] = gpu_state_read(gpu_state_start())
+        if args.full:
+            out["gpu_state_under_load"] = gpu_state_read(smi)
+            out["gpu_state_after"] = gpu_state_read(gpu_state_start())
         if alt is not None:
             out["alt_fp32_modes"] = alt
         if sweep is not None:
             out["batch_sweep_clips_s"] = sweep
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             progress("per-block rates")
             out["per_block_clips_s"] = per_block_rates(model, cfg, device)
             progress("per-kernel timing (roofline)")
@@ -733,7 +780,7 @@ def main():
                 "per_kind_ms_per_step": {k: round(v[0], 3) for k, v in kinds.items()},
                 "per_symbol_ms_per_step": {k: round(v[0], 3) for k, v in
                                            sorted(symbols.items(), key=lambda kv: -kv[1][0])}}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             progress("cpu baseline")
             out["cpu_baseline"] = cpu_baseline(cfg)
         print(json.dumps(out), flush=True)

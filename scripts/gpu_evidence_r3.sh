@@ -24,12 +24,12 @@ if [ "$STAGE" = a ]; then
     rc=$?; tail -n 3 $OUT/pytest_gpu.log; [ $rc -eq 0 ] || { echo "STOP pytest rc=$rc"; exit $rc; }
   fi
   for c in $CFGS; do
-    timeout -k 10 600 python3 bench.py --config $c > $OUT/bench_$c.json 2> $OUT/bench_$c.err
+    timeout -k 10 600 python3 bench.py --full --config $c > $OUT/bench_$c.json 2> $OUT/bench_$c.err
     rc=$?; cat $OUT/bench_$c.json; [ $rc -eq 0 ] || { echo "STOP bench $c rc=$rc"; exit $rc; }
   done
   for c in $CFGS; do
     timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $OUT/stats_$c -o run --output-format csv \
-      -- python3 bench.py --config $c --steps 10 --warmup 3 --no-cpu-baseline \
+      -- python3 bench.py --full --config $c --steps 10 --warmup 3 --no-cpu-baseline \
       > $OUT/stats_bench_$c.json 2> $OUT/stats_bench_$c.err
     rc=$?; echo "stats $c rc=$rc"; [ $rc -eq 0 ] || exit $rc
   done

@@ -29,7 +29,7 @@ for r in $(seq 1 ${ROUNDS:-2}); do
   for cfg in ${BENCH_CFGS:-cfg2}; do
     for v in base ${VARIANTS:-}; do
       lv=""; [ $v = base ] || lv=$v
-      STGCN_LIB_VARIANT=$lv timeout -k 10 300 python bench.py --config $cfg --steps 20 --warmup 5 \
+      STGCN_LIB_VARIANT=$lv timeout -k 10 300 python bench.py --full --config $cfg --steps 20 --warmup 5 \
         --no-cpu-baseline --no-roofline --no-alt --no-sweep > $OUT/bench_${cfg}_${v}_$r.json \
         2> $OUT/bench_${cfg}_${v}_$r.err || { tail -5 $OUT/bench_${cfg}_${v}_$r.err; exit 1; }
       python -c "import json,sys; d=json.load(open(sys.argv[1])); print(sys.argv[2], sys.argv[3], sys.argv[4], d['value'], d['runs_clips_s'])" \

@@ -2,7 +2,7 @@
 # eager at W = 5, twice each alternating, then the per-step window probe.
 set -o pipefail
 mkdir -p gpurun_out
-F="--no-roofline --no-alt --no-cpu-baseline --no-sweep --steps 20"
+F="--full --no-roofline --no-alt --no-cpu-baseline --no-sweep --steps 20"
 for r in 1 2; do
   for v in "--warmup 5" "--warmup 40" "--warmup 5 --no-graph"; do
     timeout -k 10 240 python3 bench.py $F $v > gpurun_out/dip.json 2>/dev/null || exit 1

@@ -14,7 +14,7 @@ fi
 for c in ${CFGS:-cfg2 cfg3 cfg5}; do
   for m in graph eager; do
     extra=""; [ $m = eager ] && extra="--no-graph"
-    timeout -k 10 300 python bench.py --config $c --steps 20 --warmup 5 --no-cpu-baseline \
+    timeout -k 10 300 python bench.py --full --config $c --steps 20 --warmup 5 --no-cpu-baseline \
       --no-roofline --no-alt --no-sweep $extra > $OUT/bench_${c}_$m.json 2> $OUT/bench_${c}_$m.err \
       || { tail -n 5 $OUT/bench_${c}_$m.err; exit 1; }
     python -c "import json,sys; d=json.load(open(sys.argv[1])); print(sys.argv[2], sys.argv[3], d['value'], d['runs_clips_s'], d['loss'], d.get('step_mode'))" \

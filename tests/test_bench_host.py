@@ -46,3 +46,42 @@ def test_pmc_profile_needs_this_source_hash(tmp_path, monkeypatch):
         {"config": "cfg2", "src_sha16": "f" * 16, "hbm_bytes_per_launch": {"k": 1}}))
     data, src = bench.pmc_profile("cfg2")
     assert data["hbm_bytes_per_launch"] == {"k": 1} and src.endswith("pmc_new_cfg2.json")
+
+
+def test_dump_outputs_files_and_budget(tmp_path, monkeypatch):
+    """--dump-outputs: loss, logits and every parameter / gradient as float32
+    <name>.npy; beyond the byte budget the large arrays are cut to a sample that
+    is the same on every call, and the total stays within the budget."""
+    import numpy as np
+    import torch
+    torch.manual_seed(0)
+    model = torch.nn.Sequential(torch.nn.Linear(96, 128), torch.nn.Linear(128, 5))
+    x = torch.randn(7, 96)
+    logits = model(x)
+    loss = logits.square().mean()
+    loss.backward()
+    bench.dump_outputs(str(tmp_path / "a"), loss, logits, model)
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    want = ["loss", "logits"] + [f"{k}.{n}" for n, _ in model.named_parameters()
+                                 for k in ("param", "grad")]
+    assert names == sorted(n + ".npy" for n in want)
+    for n in names:
+        assert np.load(tmp_path / "a" / n).dtype == np.float32
+    assert np.load(tmp_path / "a" / "loss.npy").tolist() == [loss.item()]
+    assert np.array_equal(np.load(tmp_path / "a" / "logits.npy"), logits.detach().numpy())
+    assert np.array_equal(np.load(tmp_path / "a" / "grad.0.weight.npy"),
+                          model[0].weight.grad.numpy())
+    # a budget below the total: the two 96 x 128 arrays are sampled, the rest kept whole
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 40000)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), loss, logits, model)
+    total = 0
+    for n in names:
+        b, c = np.load(tmp_path / "b" / n), np.load(tmp_path / "c" / n)
+        assert np.array_equal(b, c)
+        total += b.nbytes
+    assert total <= 40000
+    w = np.load(tmp_path / "b" / "param.0.weight.npy")
+    assert w.ndim == 1 and 0 < w.size < 96 * 128
+    assert np.isin(w, model[0].weight.detach().numpy()).all()
+    assert np.load(tmp_path / "b" / "param.1.weight.npy").shape == (5, 128)

@@ -21,8 +21,10 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import GOLDEN, load_npz, rel_to_max
+from conftest import GOLDEN, fp32_pair_tol, load_npz, rel_to_max
 from oracle import ref_cpu
+
+pytestmark = pytest.mark.usefixtures("oracle_threads")
 
 
 def _spatial_fixtures():
@@ -59,10 +61,19 @@ def test_edge_importance_oracle_matches_reference():
     _check_init(p, ref)
     assert sorted(k for k in p if k.startswith("Masks.")) == sorted(
         k for k in ref["state_keys"] if k.startswith("Masks."))
-    p = {k: v.clone().requires_grad_(True) for k, v in p.items()}
-    logits = ref_cpu.Stack(p, b).forward(torch.from_numpy(ref["x"]))
-    loss = torch.nn.functional.cross_entropy(logits, torch.from_numpy(ref["labels"]))
-    loss.backward()
+    p0, b0 = p, b
+
+    def step(dtype):
+        p = {k: v.clone().to(dtype).requires_grad_(True) for k, v in p0.items()}
+        b = {k: (v.clone().to(dtype) if v.is_floating_point() else v.clone())
+             for k, v in b0.items()}
+        logits = ref_cpu.Stack(p, b).forward(torch.from_numpy(ref["x"]), dtype=dtype)
+        loss = torch.nn.functional.cross_entropy(logits, torch.from_numpy(ref["labels"]))
+        loss.backward()
+        return p, logits, loss
+
+    p64 = step(torch.float64)[0]  # the fixture's own rounding error is measured against it
+    p, logits, loss = step(torch.float32)
     assert rel_to_max(logits.detach().numpy(), ref["logits"]) < 1e-5
     assert abs(loss.item() - float(ref["loss"])) < 1e-6
     for k, v in p.items():
@@ -71,8 +82,11 @@ def test_edge_importance_oracle_matches_reference():
             continue
         if k.endswith("temporalConv.bias"):
             continue
-        got = v.grad.reshape(-1)[torch.as_tensor(ref["pidx." + k])].numpy()
-        assert rel_to_max(got, ref["gval." + k]) < 1e-4, k
+        idx = torch.as_tensor(ref["pidx." + k])
+        got = v.grad.reshape(-1)[idx].numpy()
+        err64 = rel_to_max(p64[k].grad.reshape(-1)[idx].numpy(), ref["gval." + k])
+        assert err64 < 0.1, (k, err64)  # (the stack's documented fp32 conditioning)
+        assert rel_to_max(got, ref["gval." + k]) < fp32_pair_tol(1e-4, err64), (k, err64)
 
 
 def test_edge_importance_stack_init_and_keys(pkg):
@@ -106,13 +120,19 @@ def _legacy_oracle(ref, dtype):
 def test_legacy_stgcn_oracle_matches_reference():
     ref = load_npz("legacy_stgcn.npz")
     p, b, x, probs = _legacy_oracle(ref, torch.float32)
+    p64, _, x64, _ = _legacy_oracle(ref, torch.float64)  # measures the fixture's own error
     assert rel_to_max(probs.detach().numpy(), ref["probs"]) < 1e-5
-    assert rel_to_max(x.grad.numpy(), ref["grad.x"]) < 1e-4
+    err64 = rel_to_max(x64.grad.numpy(), ref["grad.x"])
+    assert err64 < 0.1, err64  # (the stack's documented fp32 conditioning)
+    assert rel_to_max(x.grad.numpy(), ref["grad.x"]) < fp32_pair_tol(1e-4, err64), err64
     for k, v in p.items():
         if k.startswith("Masks."):
             continue
-        got = v.grad.reshape(-1)[torch.as_tensor(ref["pidx." + k])].numpy()
-        assert rel_to_max(got, ref["gval." + k]) < 1e-4, k
+        idx = torch.as_tensor(ref["pidx." + k])
+        got = v.grad.reshape(-1)[idx].numpy()
+        err64 = rel_to_max(p64[k].grad.reshape(-1)[idx].numpy(), ref["gval." + k])
+        assert err64 < 0.1, (k, err64)
+        assert rel_to_max(got, ref["gval." + k]) < fp32_pair_tol(1e-4, err64), (k, err64)
 
 
 def test_legacy_stgcn_init_and_keys(pkg):

@@ -1,15 +1,21 @@
 """Pin the oracle (oracle/ref_cpu.py) and the graph module against golden
 vectors produced by the reference itself (tests/golden/make_golden.py)."""
+import functools
+
 import numpy as np
 import pytest
 import torch
 
-from conftest import block_fixtures, load_npz, rel_to_max
+from conftest import block_fixtures, fp32_pair_tol, load_npz, rel_to_max
 from oracle import ref_cpu
 
+pytestmark = pytest.mark.usefixtures("oracle_threads")
+
 # fp32 oracle vs fp32 reference: same ops, same library -> tiny differences
-# only from thread scheduling; fp64 oracle vs fp32 reference: the fp32 noise
-# floor measured in SURVEY §8c (<= 5e-6 rel-to-max).
+# only from the summation order (CPU, thread count); fp64 oracle vs fp32
+# reference: the fp32 noise floor measured in SURVEY §8c (<= 5e-6 rel-to-max).
+# Where the fixture itself is further than that from exact arithmetic, the fp32
+# bound follows the fixture's own error (conftest.fp32_pair_tol).
 TOL_FP32 = 1e-5
 # The fp32 reference itself is off exact arithmetic by up to ~4e-5 on the
 # W-bias grad of the residual variant (BN2 right after the spatial conv makes
@@ -18,22 +24,33 @@ TOL_FP64 = 5e-5
 ATOL_ZERO_GRAD = 1e-6  # temporalConv.bias grad is analytically 0
 
 
+def _as_numpy(out):
+    return {k: v.detach().double().numpy() for k, v in out.items()}
+
+
+@functools.lru_cache(maxsize=None)
+def _block_step64(fixture):
+    """The fp64 oracle's block step on a fixture (computed once, read only)."""
+    return _as_numpy(ref_cpu.block_step(load_npz(fixture), dtype=torch.float64))
+
+
 @pytest.mark.parametrize("fixture", block_fixtures())
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
 def test_block_oracle_matches_reference(fixture, dtype):
     ref = load_npz(fixture)
-    out = ref_cpu.block_step(ref, dtype=dtype)
+    out64 = _block_step64(fixture)
+    out = out64 if dtype == torch.float64 else _as_numpy(ref_cpu.block_step(ref, dtype=dtype))
     residual = bool(ref["meta"][7])
-    for k, v in out.items():
+    for k, got in out.items():
         want = ref[k]
-        got = v.detach().double().numpy()
         if k == "grad.temporalConv.bias" and not residual:
             assert np.abs(got - want).max() < ATOL_ZERO_GRAD * max(1.0, np.abs(ref["g"]).max()), k
             continue
         if k.endswith("num_batches_tracked"):
             assert int(got) == int(want)
             continue
-        tol = TOL_FP32 if dtype == torch.float32 else TOL_FP64
+        tol = (fp32_pair_tol(TOL_FP32, rel_to_max(out64[k], want)) if dtype == torch.float32
+               else TOL_FP64)
         assert rel_to_max(got, want) < tol, (fixture, k, rel_to_max(got, want))
 
 
@@ -47,7 +64,10 @@ def test_stack_init_matches_reference_init():
         assert abs(flat.double().sum().item() - float(ref["psum." + k])) <= 1e-9 * max(1, abs(float(ref["psum." + k])))
 
 
+@functools.lru_cache(maxsize=None)
 def _stack_step(dtype):
+    """(fixture, logits, loss, worst error, {param: (norm error, sampled error)})
+    of the oracle's stack step in ``dtype`` (computed once, read only)."""
     ref = load_npz("stack_cfg1.npz")
     A = torch.from_numpy(load_npz("adjacency.npz")["V18_s0_d1"])
     p, b = ref_cpu.init_stack_params(3, 2, A, seed=0)
@@ -57,7 +77,7 @@ def _stack_step(dtype):
     logits = st.forward(torch.from_numpy(ref["x"]), dtype=dtype)
     loss = torch.nn.functional.cross_entropy(logits, torch.from_numpy(ref["labels"]))
     loss.backward()
-    worst = 0.0
+    worst, errs = 0.0, {}
     for k, v in p.items():
         got = v.grad.reshape(-1)
         if k.endswith("temporalConv.bias"):
@@ -65,17 +85,24 @@ def _stack_step(dtype):
             continue
         gn = float(ref["gnorm." + k])
         sampled = got[torch.as_tensor(ref["pidx." + k])].numpy()
-        worst = max(worst, abs(got.norm().item() - gn) / gn,
-                    rel_to_max(sampled, ref["gval." + k]))
-    return ref, logits, loss, worst
+        errs[k] = (abs(got.norm().item() - gn) / gn, rel_to_max(sampled, ref["gval." + k]))
+        worst = max(worst, *errs[k])
+    return ref, logits.detach(), loss.detach(), worst, errs
 
 
 def test_stack_forward_backward_matches_reference():
-    """fp32 oracle vs the fp32 reference: same ops in the same order."""
-    ref, logits, loss, worst = _stack_step(torch.float32)
-    assert rel_to_max(logits.detach().numpy(), ref["logits"]) < 1e-5
+    """fp32 oracle vs the fp32 reference: same ops, the summation order the
+    CPU's; 1e-4 per parameter, or what the fixture's own distance from fp64
+    arithmetic allows where that is larger (conftest.fp32_pair_tol)."""
+    ref, logits, loss, _, errs = _stack_step(torch.float32)
+    errs64 = _stack_step(torch.float64)[4]
+    assert rel_to_max(logits.numpy(), ref["logits"]) < 1e-5
     assert abs(loss.item() - float(ref["loss"])) < 1e-6
-    assert worst < 1e-4, worst
+    for k, (norm_err, samp_err) in errs.items():
+        # the fixture's rounding noise on this gradient: the larger of its two
+        # measurements (the norm is one scalar, whose error can fall near 0 by chance)
+        tol = fp32_pair_tol(1e-4, max(errs64[k]))
+        assert norm_err < tol and samp_err < tol, (k, norm_err, samp_err, errs64[k])
 
 
 def test_stack_fp32_conditioning_is_documented():
@@ -85,8 +112,8 @@ def test_stack_fp32_conditioning_is_documented():
     the loss invariant to the scale of A). This bounds what any fp32
     implementation (including the HIP one) can match at stack level; block-level
     parity is where the tight 1e-5 gate applies (Parity)."""
-    ref, logits, loss, worst = _stack_step(torch.float64)
-    assert rel_to_max(logits.detach().numpy(), ref["logits"]) < 1e-4
+    ref, logits, loss, worst, _ = _stack_step(torch.float64)
+    assert rel_to_max(logits.numpy(), ref["logits"]) < 1e-4
     assert abs(loss.item() - float(ref["loss"])) < 1e-5
     assert 1e-4 < worst < 0.1, worst
 
