@@ -92,8 +92,7 @@ extern "C" {
                             * (with the SpatialConv backward fused into it); BN1's
                             * nearly cancelling sum of dxhat (its bias gradient) is
                             * formed from the fp64 per-tap dU sums instead of from the
-                            * 22-bit data gradient. (The 3-way bf16 data gradient is an
-                            * A/B measurement build only: STGCN_AB_F16X2_DGRAD=0.) At
+                            * 22-bit data gradient. At
                             * V = 25 (folded, K = 1) the data gradient stays on the
                             * 3-way bf16 splits. ABI 8: an unfolded non-residual V = 18,
                             * K = 1 block with C_out >= 16 (the first block, C_in = 3)

@@ -17,8 +17,9 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall"]
 
 
 def build(verbose=False, variant=None, defines=()):
-    """variant: build lib/libstgcn_hip_<variant>.so with extra -D defines (A/B
-    kernel experiments, loaded with STGCN_LIB_VARIANT=<variant>)."""
+    """variant: build lib/libstgcn_hip_<variant>.so with extra -D defines, e.g.
+    build(variant="exp", defines=("MY_EXPERIMENT=1",)) for a kernel experiment
+    that adds its own switch; loaded with STGCN_LIB_VARIANT=<variant>."""
     out = OUT if variant is None else os.path.join(os.path.dirname(OUT),
                                                    f"libstgcn_hip_{variant}.so")
     objdir = os.path.join(HERE, "build", variant or "default")

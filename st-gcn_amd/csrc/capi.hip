@@ -74,8 +74,8 @@ size_t wpk_floats(const stgcn_desc_t *d) {
   // the fused bf16 spatial forward: packed W' + the A image
   if (d->flags & STGCN_F_BF16)
     n = std::max(n, (sp_fwd_bf16_wpk_bytes(d->C_in, d->C_out, d->K, d->V) + 3) / 4);
-  // the fused spatial backward: packed W' planes + its A image
-  if (d->flags & (STGCN_F_BF16 | STGCN_F_F32X3))
+  // the fused spatial backward: packed W' + its A image
+  if (d->flags & STGCN_F_BF16)
     n = std::max(n, (sp_bwd_fused_wpk_bytes(d->C_in, d->C_out, d->K, d->V) + 3) / 4);
   return n;
 }
@@ -96,18 +96,17 @@ Dropout make_dropout(const stgcn_desc_t *d, float p, uint64_t seed) {
   dr.scale = p < 1.f ? (float)(1.0 / (1.0 - (double)p)) : 0.f;
   return dr;
 }
-// the fused spatial forward (kernels_fused.hip) of the bf16 path applies
-// (STGCN_AB_UNFUSED_SP build: the unfused gather + GEMM kernels, A/B measurement only)
+// the fused spatial forward (kernels_fused.hip) of the bf16 path applies (other
+// shapes: the unfused gather + GEMM kernels)
 bool fused_sp(const stgcn_desc_t *d) {
-  constexpr bool off = STGCN_AB_UNFUSED_SP != 0;
-  return !off && bf16(d) && sp_fwd_bf16_supported(d->C_in, d->V, d->K, d->C_out, residual(d));
+  return bf16(d) && sp_fwd_bf16_supported(d->C_in, d->V, d->K, d->C_out, residual(d));
 }
-// the fused spatial backward (kernels_spbwd.hip) applies: bf16 path, or the fp32
-// split path (STGCN_AB_UNFUSED_SPB build: the H GEMM + k_spatial_bwd5/6 pair, A/B only)
+// the fused spatial backward (kernels_spbwd.hip) applies: bf16 path only (other
+// shapes, and the fp32 split path: the H GEMM + k_spatial_bwd5/6 pair, which at
+// K = 1 measured faster than an exact-split fused kernel, cfg2 L1 281 vs 351 us)
 bool fused_spb(const stgcn_desc_t *d) {
-  constexpr bool off = STGCN_AB_UNFUSED_SPB != 0;
-  return !off && (bf16(d) || f32x3(d)) &&
-         sp_bwd_fused_supported(d->C_in, d->V, d->K, d->C_out, d->T, f32x3(d));
+  return bf16(d) && !f32x3(d) &&
+         sp_bwd_fused_supported(d->C_in, d->V, d->K, d->C_out, d->T);
 }
 // the fused backward of the two-person graph: two kernels (k_sp50_dx, k_sp50_dA),
 // timed apart as which 5 / 6
@@ -119,20 +118,17 @@ bool fused_spb50(const stgcn_desc_t *d) { return fused_spb(d) && d->V == 50; }
 // fp32 split path, K = 1: V = 18 (cfg2) and V = 25 (the reference's default
 // L_STGCN graph: NTU joints, unilabeling partition, lightning_model.py:271),
 // non-residual blocks over >= 16 input and output channels (the data gradient
-// reduces over C_out: k_conv_x3 needs >= 16 there) (STGCN_AB_NO_FOLD build: the
-// unfolded kernels, A/B only).
+// reduces over C_out: k_conv_x3 needs >= 16 there); every other block runs the
+// unfolded kernels.
 bool fold_w(const stgcn_desc_t *d) {
-  constexpr bool off = STGCN_AB_NO_FOLD != 0;
-  return !off && f32x3(d) && !residual(d) && d->K == 1 && d->C_in >= 16 && d->C_out >= 16 &&
-         (d->V == 18 || d->V == 25) && !fused_spb(d);
+  return f32x3(d) && !residual(d) && d->K == 1 && d->C_in >= 16 && d->C_out >= 16 &&
+         (d->V == 18 || d->V == 25);
 }
 // The folded block's SpatialConv backward inside its data gradient (kernels_x3.hip
 // spb_epilogue, V = 18): dxhat = H A, dA, the BN1 / chain sums from the tile
-// while H is on chip. V = 25 (and the STGCN_AB_SPB_PAIR build): the data gradient
-// stores H and the unfused spatial backward (k_spatial_bwd5) reads it.
-bool fold_spb(const stgcn_desc_t *d) {
-  return fold_w(d) && d->V == 18 && STGCN_AB_SPB_PAIR == 0;
-}
+// while H is on chip. V = 25: the data gradient stores H and the unfused spatial
+// backward (k_spatial_bwd5) reads it.
+bool fold_spb(const stgcn_desc_t *d) { return fold_w(d) && d->V == 18; }
 
 // The folded block's temporal GEMMs on 2-way fp16 splits (STGCN_F_F16X2; k_conv_x3 /
 // k_wgrad_x3 with NPL = 2), operand scales from max |x| words (launch_absmax)
@@ -151,12 +147,10 @@ bool f16x2_tw(const stgcn_desc_t *d) { return f16x2(d) || f16x2_unfold(d); }
 // elements of a zero-mean dU (heavy cancellation; the 2^-22 operand
 // representation measured 2.5x the fp32 reference's own error on the BN1 bias
 // gradient at N = 32, T = 300), which the folded block takes from the fp64 dU
-// sums instead (kernels_fold.hip k_fold_sd). STGCN_AB_F16X2_DGRAD=0 build: the
-// 3-way bf16 splits there (A/B only).
-// (only where BN1's sum comes from the fp64 dU sums: the fused backward, fold_spb)
-bool f16x2_dgrad(const stgcn_desc_t *d) {
-  return f16x2(d) && fold_spb(d) && STGCN_AB_F16X2_DGRAD != 0;
-}
+// sums instead (kernels_fold.hip k_fold_sd).
+// (only where BN1's sum comes from the fp64 dU sums: the fused backward, fold_spb;
+// elsewhere the data gradient stays on the 3-way bf16 splits)
+bool f16x2_dgrad(const stgcn_desc_t *d) { return f16x2(d) && fold_spb(d); }
 // ... and G never formed (north star N1; kernels_x3.hip bna_contract): the
 // forward GEMM reads x, applies BN1 in its window loader and the joint
 // contraction with A in its epilogue (U = A U' + BT), the weight gradient reads
@@ -204,32 +198,13 @@ bool x_from_u(const stgcn_desc_t *d) {
 // sum_{n,t} dZ of the non-residual block from per-tap sums of dU (clip-chunk
 // sums written by the ReLU + BN2 backward apply, k_fold_tq, one small GEMM with
 // Wt) instead of a pass over dZ (the folded block has no dZ at all): cfg3 5632
-// vs 5604, cfg5 2658 vs 2631 clips/s in one A/B call (STGCN_AB_SUM_NT build:
-// the pass over dZ on unfolded blocks, A/B only).
-bool cols_sums(const stgcn_desc_t *d) {
-  return !residual(d) && (fold_w(d) || STGCN_AB_SUM_NT == 0);
-}
+// vs 5604, cfg5 2658 vs 2631 clips/s in one A/B call. Residual blocks still
+// make the pass over dZ.
+bool cols_sums(const stgcn_desc_t *d) { return !residual(d); }
 // The folded forward leaves Wc in the (otherwise unused) Z buffer for the
 // backward when it fits (Z is opaque to the caller under STGCN_F_F32X3 then)
 bool fold_wc_in_z(const stgcn_desc_t *d) {
   return fold_w(d) && (int64_t)d->N * d->C_out * d->T * d->V >= (int64_t)d->C_out * d->C_in * 9;
-}
-// Clips per slice of the unfused spatial backward (H GEMM + joint kernel). The
-// shipped build runs the whole batch as one slice. STGCN_AB_SLICE build (A/B
-// only): the slice's H, dZ, x and dx (fp32) within ~160 MiB, so the Infinity
-// Cache (256 MiB; MI355X_MICROARCH.md) could serve H's read-back -- measured
-// SLOWER in one A/B call (round 3: cfg5 2126 vs 2324, cfg2 4182 vs 4432 clips/s):
-// the persistent joint kernels (k_spatial_bwd5/6) flush their dA accumulators
-// and BN1 sums once per launch, so 16 launches per layer (8-clip slices at cfg5)
-// multiply that tail and underfill the grid.
-int spatial_bwd_slice(const stgcn_desc_t *d) {
-  constexpr bool on = STGCN_AB_SLICE != 0;
-  if (!on) return d->N;
-  const int64_t per_clip =
-      (int64_t)4 * d->T * d->V * ((int64_t)d->K * d->C_in + d->C_out + 2 * d->C_in);
-  const int64_t budget = (int64_t)160 << 20;
-  const int ns = (int)std::max<int64_t>(8, budget / std::max<int64_t>(per_clip, 1));
-  return std::min(ns, d->N);
 }
 // residual block with a 1x1 projection (apply_residual Conv2d, st_graphconv.py:27)
 bool projection(const stgcn_desc_t *d) {
@@ -280,7 +255,7 @@ WgradParams make_wgrad(const stgcn_desc_t *d, const float *P, int64_t pb, int R,
   if (wgrad_sp_applies(w)) plan_wgrad_sp(w);
   if (bf16(d)) plan_wgrad_bf16(w);  // k_wgrad_bf16 where it covers the shape
   // fp32 path of STGCN_F_F32X3: the spatial dW' on exact bf16 splits (k_wgrad_sp<.., X3>)
-  if (f32x3(d) && wgrad_sp_applies(w) && !STGCN_AB_WSP_F32) w.bf16 = 3;
+  if (f32x3(d) && wgrad_sp_applies(w)) w.bf16 = 3;
   return w;
 }
 
@@ -576,15 +551,15 @@ bool prep_applies(const stgcn_desc_t *d) {
 // the bytes move; the bias / BN gradients use the fp32 sums of the producing
 // passes. The tensors keep their fp32-sized buffers (the first half holds the
 // bf16 data). Producers: the fused spatial forward's epilogues (so C_in >= 16)
-// and the BN2 + ReLU backward pass. (STGCN_AB_ACT_FP32 build: fp32 storage, A/B only)
+// and the BN2 + ReLU backward pass. (fp32 storage there measured slower: cfg3
+// 5,831 vs 5,948 and cfg5 2,528 vs 2,731 clips/s.)
 bool act_bf16(const stgcn_desc_t *d) {
-  constexpr bool off = STGCN_AB_ACT_FP32 != 0 || STGCN_AB_GENERIC_CONV != 0;
   // Stride-2 blocks at odd V keep fp32: their weight gradient (k_wgrad_bf16<9,V,2>)
   // staged bf16 pairs by registers slower than fp32 (cfg5 2.19 -> 2.66 ms per
   // step), more than the strided forward and data-gradient phases gained; at even
-  // V it stages them by LDS-DMA (STGCN_AB_S2_ACT_FP32 build: fp32 there, A/B only).
-  const bool s2 = d->stride == 2 && d->V % 2 == 0 && STGCN_AB_S2_ACT_FP32 == 0;
-  if (off || !fused_sp(d) || residual(d) || (d->stride != 1 && !s2)) return false;
+  // V it stages them by LDS-DMA (fp32 there: cfg5 2592 vs 2644 clips/s).
+  const bool s2 = d->stride == 2 && d->V % 2 == 0;
+  if (!fused_sp(d) || residual(d) || (d->stride != 1 && !s2)) return false;
   ConvGemmParams p = conv_base(d, nullptr);  // the temporal conv forward and data gradient
   p.C = d->C_out;
   p.R = d->C_out;
@@ -597,39 +572,9 @@ bool act_bf16(const stgcn_desc_t *d) {
 bool z_bf16(const stgcn_desc_t *d) { return act_bf16(d); }
 bool du_bf16(const stgcn_desc_t *d) { return act_bf16(d); }
 
-// dZ (the gradient at the SpatialConv output) stored in bf16 on the bf16 path's
-// non-residual blocks whose dW' reads the kept bf16 G: its readers round dZ to
-// bf16 anyway (k_sp_bwd_fused's H GEMM operand -- or, unfused, the H GEMM
-// k_conv_bf16<1, .., IB> -- and k_wgrad_gemm_gk's P operand), so they see the
-// same values at half the bytes (and the fused kernel's ring is 6 chunks deep
-// instead of 4); the remaining reader, the bias-type sums sum_{n,t} dZ
-// (k_sum_nt4_bf16), accumulates the bf16 values in fp64. Producer: the temporal
-// data-gradient (one-plane k_conv_x3, bf16 epilogue store). The buffer keeps
-// its fp32 size.
-// Not the shipped default: measured in one A/B call (round 3) fp32 dZ ran cfg3
-// 5415 vs 5285 and cfg5 2137 vs 2126 clips/s, so bf16 dZ is the STGCN_AB_DZ_BF16
-// build only (A/B measurement).
-bool dz_bf16(const stgcn_desc_t *d) {
-  constexpr bool on = STGCN_AB_DZ_BF16 != 0;
-  if (!on || !bf16(d) || residual(d) || !fused_sp(d)) return false;
-  if (fused_spb(d) && d->V == 50) return false;  // (k_sp50_dx / _dA read fp32 dZ)
-  if (!fused_spb(d)) {  // the unfused spatial backward: its H GEMM reads dZ (k_conv_bf16<.., IB>)
-    ConvGemmParams h = conv_base(d, nullptr);
-    h.C = d->C_out;
-    h.R = d->K * d->C_in;
-    h.NQ = 1;
-    h.s_in = 1;
-    if (!conv_bf16_supported(h)) return false;
-  }
-  ConvGemmParams p = conv_base(d, nullptr);  // the data gradient's launch(es)
-  p.C = d->C_out;
-  p.R = d->C_out;
-  p.s_in = 1;
-  p.NQ = d->stride == 1 ? 9 : 5;
-  if (!conv_b1_supported(p)) return false;
-  p.NQ = 4;
-  return d->stride == 1 || conv_b1_supported(p);
-}
+// dZ (the gradient at the SpatialConv output) stays in fp32 on every path:
+// bf16 storage measured slower in one A/B call (cfg3 5285 vs 5415, cfg5 2126 vs
+// 2137 clips/s).
 
 }  // namespace
 
@@ -1217,8 +1162,6 @@ int stgcn_block_bwd(const stgcn_desc_t *d, const stgcn_bwd_args_t *a, void *work
                                 nullptr, s));
   }
 
-  // dZ in bf16 where every reader takes it (needs the kept G: k_wgrad_gemm_gk)
-  const bool dzb = dz_bf16(d) && a->G != nullptr;
   // Deferred dx (ABI 5): the BN1 backward apply of this block is folded into the
   // previous block's ReLU+BN2 backward apply (launch_bn_relu_bwd_apply with
   // dy_coef). The spatial backward then reads the previous block's U in place of
@@ -1391,7 +1334,6 @@ int stgcn_block_bwd(const stgcn_desc_t *d, const stgcn_bwd_args_t *a, void *work
     p.in = L.dU;
     p.in_bf16 = du_bf16(d) ? 1 : 0;
     p.out = L.dZ;
-    p.out_bf16 = dzb ? 1 : 0;
     p.in_bstride = (int64_t)R * To * V;
     p.out_bstride = (int64_t)R * T * V;
     p.w_sr = 9;
@@ -1474,7 +1416,6 @@ int stgcn_block_bwd(const stgcn_desc_t *d, const stgcn_bwd_args_t *a, void *work
     w.T_src = T;
     w.V = V;
     w.N = N;
-    w.p_bf16 = dzb ? 1 : 0;
     plan_wgrad_gk(w, T);
     HIP_TRY(launch_wgrad_gk(w, s));
     HIP_TRY(launch_slab_reduce(L.slab, w.S, (int64_t)R * K * C, a->dW, 1, R, K, C, s));
@@ -1490,7 +1431,7 @@ int stgcn_block_bwd(const stgcn_desc_t *d, const stgcn_bwd_args_t *a, void *work
     HIP_TRY(launch_wgrad(w, s));
     HIP_TRY(launch_slab_reduce(L.slab, w.S, (int64_t)R * K * C, a->dW, 1, R, K, C, s));
   }
-  if (!cols_sums(d)) HIP_TRY(launch_sum_nt(L.dZ, N, R, T, V, L.SdZ, s, dzb ? 1 : 0));
+  if (!cols_sums(d)) HIP_TRY(launch_sum_nt(L.dZ, N, R, T, V, L.SdZ, s));
   }
   // sum_{n,t} dZ: from the temporal weight and the per-tap dU sums on the
   // non-residual block (dZ = conv^T(dU)); the residual block's dZ passes BN2
@@ -1506,31 +1447,21 @@ int stgcn_block_bwd(const stgcn_desc_t *d, const stgcn_bwd_args_t *a, void *work
     // H = W'^T dZ, dx = sum_k H_k A_k, dA, BN1 sums in one kernel (H stays on chip)
     HIP_TRY(launch_sp_bwd_fused(L.dZ, xin, mean1, invstd1, a->g1, a->b1, a->A, a->W, L.wpk,
                                 a->dx, a->dA, L.sd, L.sdn, N, C, R, T, V, K, d->need_dx, res,
-                                f32x3(d), s, defer ? &pvb : nullptr, dzb ? 1 : 0));
+                                s, defer ? &pvb : nullptr));
   } else {
-  // Clip slices (spatial_bwd_slice): the H GEMM and the joint kernel run on ns
-  // clips at a time, so the slice of H they hand over (and the dZ / x / dx
-  // slices around it) stay within the 256 MiB Infinity Cache: H is written and
-  // read back on-die instead of through HBM (the buffer is reused per slice).
-  const float *Wz = a->W;
-  if (K > 1) {
-    HIP_TRY(launch_pack_w(a->W, L.Wpk, K, R, C, s));
-    Wz = L.Wpk;
-  }
-  const int NSL = spatial_bwd_slice(d);
-  int64_t sparts = 0;  // (deterministic dA: the joint kernel's workgroup partials, if it takes them)
-  for (int n0 = 0; n0 < N; n0 += NSL) {
-  const int ns = std::min(NSL, N - n0);
-  const int64_t xo = (int64_t)n0 * C * T * V;
+  // The H GEMM and the joint kernel run over the whole batch at once (clip
+  // slices sized to the Infinity Cache measured slower: cfg5 2126 vs 2324 clips/s,
+  // the persistent joint kernels flush dA and the BN1 sums once per launch).
   if (!fold_w(d)) {  // (the folded block's data gradient wrote H)
     // H = W'^T dZ for all partitions in one GEMM (rows k*C_in + ci of H are
     // the channels of H_k): dZ is read once instead of K times
+    const float *Wz = a->W;
+    if (K > 1) {
+      HIP_TRY(launch_pack_w(a->W, L.Wpk, K, R, C, s));
+      Wz = L.Wpk;
+    }
     ConvGemmParams p = conv_base(d, L.wpk);
-    p.N = ns;
-    p.in_bf16 = dzb ? 1 : 0;  // (element offsets: the bf16 kernel halves them)
-    p.in = dzb ? reinterpret_cast<const float *>(reinterpret_cast<const __bf16 *>(L.dZ) +
-                                                 (int64_t)n0 * R * T * V)
-               : L.dZ + (int64_t)n0 * R * T * V;
+    p.in = L.dZ;
     p.w = Wz;
     p.out = L.H;
     p.in_bstride = (int64_t)R * T * V;
@@ -1551,14 +1482,11 @@ int stgcn_block_bwd(const stgcn_desc_t *d, const stgcn_bwd_args_t *a, void *work
     conv_tiles(p);
     HIP_TRY(launch_conv_gemm(p, s));
   }
-  int64_t np = 0;
-  HIP_TRY(launch_spatial_dx(L.H, xin + xo, mean1, invstd1, a->g1, a->b1, a->A,
-                            a->dx ? a->dx + xo : nullptr, a->dA, L.sd, L.sdn, ns, C, T, V, K,
-                            d->need_dx, res, bf16(d) ? 1 : 0, s, defer ? &pvb : nullptr,
-                            L.dApart ? L.dApart + sparts * K * V * V : nullptr,
-                            L.dA_cap - sparts, &np));
-  sparts += np;
-  }
+  // (deterministic dA: the joint kernel's workgroup partials, if it takes them)
+  int64_t sparts = 0;
+  HIP_TRY(launch_spatial_dx(L.H, xin, mean1, invstd1, a->g1, a->b1, a->A, a->dx, a->dA, L.sd,
+                            L.sdn, N, C, T, V, K, d->need_dx, res, bf16(d) ? 1 : 0, s,
+                            defer ? &pvb : nullptr, L.dApart, L.dA_cap, &sparts));
   HIP_TRY(launch_dA_reduce(L.dApart, sparts, K * V * V, L.dAlvl, a->dA, s));
   }
   if (defer) {
@@ -1735,7 +1663,6 @@ TimedPlan plan_timed(const stgcn_desc_t *d, int which, void *scratch) {
     p.in_bf16 = du_bf16(d) ? 1 : 0;
     const float *w = c.take<float>((size_t)R * CZ * 9);
     p.out = c.take<float>((size_t)N * CZ * T * V);
-    p.out_bf16 = dz_bf16(d) ? 1 : 0;  // (the stack keeps G, so dZ is bf16 there)
     p.in_bstride = (int64_t)R * To * V;
     p.out_bstride = (int64_t)CZ * T * V;
     p.w_sr = 9;
@@ -1839,7 +1766,6 @@ TimedPlan plan_timed(const stgcn_desc_t *d, int which, void *scratch) {
     if (!fused_spb(d) && !fold) {
       ConvGemmParams p = conv_base(d, wpk);
       p.in = P.dZ;
-      p.in_bf16 = dz_bf16(d) ? 1 : 0;
       p.w = c.take<float>((size_t)R * K * C);  // (the packed W' of the block)
       p.out = P.H;
       p.in_bstride = (int64_t)R * T * V;
@@ -1939,8 +1865,7 @@ int stgcn_time_kernel(const stgcn_desc_t *d, int which, void *scratch, size_t sc
       if (fused_spb(d))
         return launch_sp_bwd_fused(P.dZ, P.x, P.st, P.st + C, P.st + 2 * C, P.st + 3 * C, P.A,
                                    P.W, P.wpk, P.dx, P.dA, P.sd, P.sd + C, d->N, C, d->C_out,
-                                   d->T, d->V, d->K, 1, residual(d) ? 1 : 0, f32x3(d), s,
-                                   nullptr, dz_bf16(d) ? 1 : 0,
+                                   d->T, d->V, d->K, 1, residual(d) ? 1 : 0, s, nullptr,
                                    P.spb_gemm && P.spb_joint ? 0 : (P.spb_gemm ? 1 : 2));
       if (P.spb_gemm) {
         hipError_t e = launch_conv_gemm(P.cp[0], s);

@@ -3,7 +3,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "ab_switches.h"
 
 namespace stgcn {
 
@@ -368,7 +367,7 @@ hipError_t launch_gather_fwd(const float *x, const float *mean, const float *inv
 // k_gather4 only: K = 1, 16-byte aligned x / G and these shapes
 bool gather_prev_supported(int C, int T, int V);
 hipError_t launch_sum_nt(const float *X, int N, int C, int T, int V, double *out,
-                         hipStream_t s, int x_bf16 = 0);
+                         hipStream_t s);
 hipError_t launch_spatial_small(const double *SdZ, const float *A, const float *bW, int K,
                                 int R, int V, float *dbW, float *dA, hipStream_t s);
 hipError_t launch_spatial_dx(const float *H, const float *x, const float *mean,
@@ -409,15 +408,14 @@ hipError_t launch_wgrad_gk(const WgradParams &p, hipStream_t s);
 // dx (BN1 input side, before the BN1 backward apply), dA += sum H_k^T f(BN1(x))
 // and the BN1 backward sums, H = W'^T dZ never in HBM. wpk: scratch of
 // sp_bwd_fused_wpk_bytes (packed W' + the A image).
-// x3: the fp32 path of STGCN_F_F32X3 (exact bf16 splits) instead of the bf16 path
-bool sp_bwd_fused_supported(int C, int V, int K, int R, int T, bool x3);
+bool sp_bwd_fused_supported(int C, int V, int K, int R, int T);
 size_t sp_bwd_fused_wpk_bytes(int C, int R, int K, int V);
 hipError_t launch_sp_bwd_fused(const float *dZ, const float *x, const float *mean,
                                const float *invstd, const float *g, const float *b,
                                const float *A, const float *W, void *wpk, float *dx, float *dA,
                                double *sd, double *sdn, int N, int C, int R, int T, int V, int K,
-                               int write_dx, int relu, bool x3, hipStream_t s,
-                               const PrevBn *prev = nullptr, int dz_bf16 = 0, int only = 0);
+                               int write_dx, int relu, hipStream_t s,
+                               const PrevBn *prev = nullptr, int only = 0);
 // V = 50 runs the fused backward as two kernels (k_sp50_dx, k_sp50_dA); only = 1 / 2
 // launches just the first / second of them (timing entry point), 0 both.
 

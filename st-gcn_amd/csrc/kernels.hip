@@ -275,10 +275,7 @@ struct ConvGeo {
   static constexpr int BUF = WBUF + IBUF;               // floats per ring slot
   // ring depth: 3 slots (the short spatial chunks too: 2 slots measured 4-5%
   // slower at the cfg2 layer shapes once bias_rv moved to LDS)
-#ifndef STGCN_STAGES1
-#define STGCN_STAGES1 3
-#endif
-  static constexpr int STAGES = NQ == 1 ? STGCN_STAGES1 : 3;
+  static constexpr int STAGES = 3;
   static_assert((STAGES - 2) * DPW < 64, "vmcnt range");
   // Input stride 2: each channel's window is stored de-interleaved, even
   // frames first (NFE of them) then odd frames, so output column (mf, v) at
@@ -376,7 +373,7 @@ __global__ __launch_bounds__(256, 2) void k_tconv(ConvGemmParams p) {
     if (c < nchunks) stage(c, wbuf(c), ibuf(c));
   auto body = [&](int chunk, auto slot_c) {
     constexpr int SLOT = decltype(slot_c)::value;
-    if (S == 3 && chunk + 1 < nchunks)  // chunk c+1 may stay in flight
+    if (chunk + 1 < nchunks)  // chunk c+1 may stay in flight
       asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"((S - 2) * G::DPW) : "memory");
     else
       asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
@@ -412,12 +409,11 @@ __global__ __launch_bounds__(256, 2) void k_tconv(ConvGemmParams p) {
       __builtin_amdgcn_sched_barrier(0);
     }
   };
-  static_assert(S == 2 || S == 3, "ring depth");
+  static_assert(S == 3, "ring depth");
   for (int chunk = 0; chunk < nchunks; chunk += S) {
     body(chunk, std::integral_constant<int, 0>{});
     if (chunk + 1 < nchunks) body(chunk + 1, std::integral_constant<int, 1>{});
-    if constexpr (S == 3)
-      if (chunk + 2 < nchunks) body(chunk + 2, std::integral_constant<int, 2 % S>{});
+    if (chunk + 2 < nchunks) body(chunk + 2, std::integral_constant<int, 2>{});
   }
   asm volatile("s_barrier" ::: "memory");  // every wave done reading the ring (LDS reuse)
 
@@ -431,25 +427,19 @@ __global__ __launch_bounds__(256, 2) void k_tconv(ConvGemmParams p) {
 // the joint counts of the reference's skeleton graphs (coco18, body25,
 // two-person body25), input stride 1 (and 2 for the strided temporal forward).
 static bool tconv_specialised(const ConvGemmParams &p) {
-  if (STGCN_AB_GENERIC_CONV) return false;  // A/B builds only (ab_switches.h)
   if (p.V != 18 && p.V != 25 && p.V != 50) return false;
   if (p.FT != kTileCols / p.V) return false;
   if (p.s_in == 2) return p.NQ == 9;
   return p.s_in == 1 && (p.NQ == 1 || p.NQ == 4 || p.NQ == 5 || p.NQ == 9);
 }
 
-// Channels per reduction chunk. Specialised kernels: 8 for the spatial GEMM
-// (2-slot ring), 2 for the temporal taps (3-slot ring, 27 KB of LDS: 4
-// workgroups per CU); measured against 16/32 and 4/6/8 (scripts/ck_sweep.sh).
-#ifndef STGCN_CK1
-#define STGCN_CK1 8
-#endif
-#ifndef STGCN_CK45
-#define STGCN_CK45 2
-#endif
+// Channels per reduction chunk. Specialised kernels: 8 for the spatial GEMM,
+// 2 for the temporal taps (3-slot ring, 27 KB of LDS: 4 workgroups per CU);
+// measured against 16/32 and 4/6/8.
+constexpr int kCk1 = 8, kCkTaps = 2;
 static int conv_ck(const ConvGemmParams &p) {
   if (!tconv_specialised(p)) return p.NQ == 1 ? 32 : 8;
-  return p.NQ == 1 ? STGCN_CK1 : (p.NQ == 4 || p.NQ == 5) ? STGCN_CK45 : 2;
+  return p.NQ == 1 ? kCk1 : kCkTaps;
 }
 
 int conv_gemm_cpad(const ConvGemmParams &p) {
@@ -470,7 +460,7 @@ size_t conv_gemm_lds_bytes(const ConvGemmParams &p) {
     const int WROWS = (CK * p.NQ * 64 + 255) / 256;
     const int IROWS = round64(CK * (conv_gemm_span(p) | 1)) / 64;
     const int DPW = (WROWS + IROWS + 3) / 4;
-    const int stages = p.NQ == 1 ? STGCN_STAGES1 : 3;
+    constexpr int stages = 3;  // ConvGeo::STAGES
     return sizeof(float) * stages * ((size_t)WROWS * 256 + (size_t)(4 * DPW - WROWS) * 64);
   }
   const size_t stats = sizeof(double) * 4 * 16 * 2 * 64;  // k_conv_gemm epilogue buffer
@@ -501,19 +491,6 @@ static bool launch_tconv_v(const ConvGemmParams &p, int nblk, size_t lds, hipStr
   return false;
 }
 
-template <int NQ>
-static bool launch_tconv_ck(const ConvGemmParams &p, int CK, int nblk, size_t lds,
-                            hipStream_t s) {
-  if constexpr (NQ == 1) {
-    if (CK == STGCN_CK1) return launch_tconv_v<NQ, STGCN_CK1>(p, nblk, lds, s);
-  } else if constexpr (NQ == 4 || NQ == 5) {
-    if (CK == STGCN_CK45) return launch_tconv_v<NQ, STGCN_CK45>(p, nblk, lds, s);
-  } else {
-    if (CK == 2) return launch_tconv_v<NQ, 2>(p, nblk, lds, s);
-  }
-  return false;
-}
-
 hipError_t launch_conv_gemm(const ConvGemmParams &p0, hipStream_t s) {
   // (per-tile statistics partials: k_conv_x3's row-major epilogue only)
   if (p0.stat_part && (p0.s_out != 1 || !p0.stat_sum)) return hipErrorInvalidValue;
@@ -536,20 +513,19 @@ hipError_t launch_conv_gemm(const ConvGemmParams &p0, hipStream_t s) {
   const int nblk = p.N * p.n_mtiles * p.n_rtiles;
   const size_t lds = conv_gemm_lds_bytes(p);
   if (tconv_specialised(p)) {
-    const int CK = conv_ck(p);
-    bool done = false;
+    bool done = false;  // (chunk channels as conv_ck)
     switch (p.NQ) {
       case 1:
-        done = launch_tconv_ck<1>(p, CK, nblk, lds, s);
+        done = launch_tconv_v<1, kCk1>(p, nblk, lds, s);
         break;
       case 4:
-        done = launch_tconv_ck<4>(p, CK, nblk, lds, s);
+        done = launch_tconv_v<4, kCkTaps>(p, nblk, lds, s);
         break;
       case 5:
-        done = launch_tconv_ck<5>(p, CK, nblk, lds, s);
+        done = launch_tconv_v<5, kCkTaps>(p, nblk, lds, s);
         break;
       case 9:
-        done = launch_tconv_ck<9>(p, CK, nblk, lds, s);
+        done = launch_tconv_v<9, kCkTaps>(p, nblk, lds, s);
         break;
     }
     return done ? hipGetLastError() : hipErrorInvalidValue;
@@ -1018,27 +994,21 @@ hipError_t launch_wgrad_taps(const WgradParams &p, hipStream_t s) {
   if (!wgrad_taps_supported(p)) return hipErrorInvalidValue;
   const int nblk = p.n_rtiles * p.n_jtiles * p.S;
   const size_t lds = wgrad_taps_lds_bytes(p);
-  if (!STGCN_AB_GENERIC_CONV) {
-    // the plans make_wgrad_taps builds for the reference's graphs (FT = 80 / V,
-    // reduced until the double-buffered images fit in LDS)
-    if (p.V == 18 && p.FT == 4 && p.s_in == 1)
-      hipLaunchKernelGGL((k_wgrad_taps<64, 8, 18, 1, 4>), dim3(nblk), dim3(512), lds, s, p);
-    else if (p.V == 18 && p.FT == 3 && p.s_in == 2)
-      hipLaunchKernelGGL((k_wgrad_taps<64, 8, 18, 2, 3>), dim3(nblk), dim3(512), lds, s, p);
-    else if (p.V == 25 && p.FT == 2 && p.s_in == 1)
-      hipLaunchKernelGGL((k_wgrad_taps<64, 8, 25, 1, 2>), dim3(nblk), dim3(512), lds, s, p);
-    else if (p.V == 25 && p.FT == 1 && p.s_in == 2)
-      hipLaunchKernelGGL((k_wgrad_taps<64, 8, 25, 2, 1>), dim3(nblk), dim3(512), lds, s, p);
-    else if (p.V == 50 && p.FT == 1 && p.s_in == 1)
-      hipLaunchKernelGGL((k_wgrad_taps<32, 4, 50, 1, 1>), dim3(nblk), dim3(256), lds, s, p);
-    else if (p.V == 50 && p.FT == 1 && p.s_in == 2)
-      hipLaunchKernelGGL((k_wgrad_taps<32, 4, 50, 2, 1>), dim3(nblk), dim3(256), lds, s, p);
-    else
-      goto generic_path;
-    return hipGetLastError();
-  }
-generic_path:
-  if (wgrad_taps_cb(p) == 64)
+  // the plans make_wgrad_taps builds for the reference's graphs (FT = 80 / V,
+  // reduced until the double-buffered images fit in LDS), else the runtime-geometry kernels
+  if (p.V == 18 && p.FT == 4 && p.s_in == 1)
+    hipLaunchKernelGGL((k_wgrad_taps<64, 8, 18, 1, 4>), dim3(nblk), dim3(512), lds, s, p);
+  else if (p.V == 18 && p.FT == 3 && p.s_in == 2)
+    hipLaunchKernelGGL((k_wgrad_taps<64, 8, 18, 2, 3>), dim3(nblk), dim3(512), lds, s, p);
+  else if (p.V == 25 && p.FT == 2 && p.s_in == 1)
+    hipLaunchKernelGGL((k_wgrad_taps<64, 8, 25, 1, 2>), dim3(nblk), dim3(512), lds, s, p);
+  else if (p.V == 25 && p.FT == 1 && p.s_in == 2)
+    hipLaunchKernelGGL((k_wgrad_taps<64, 8, 25, 2, 1>), dim3(nblk), dim3(512), lds, s, p);
+  else if (p.V == 50 && p.FT == 1 && p.s_in == 1)
+    hipLaunchKernelGGL((k_wgrad_taps<32, 4, 50, 1, 1>), dim3(nblk), dim3(256), lds, s, p);
+  else if (p.V == 50 && p.FT == 1 && p.s_in == 2)
+    hipLaunchKernelGGL((k_wgrad_taps<32, 4, 50, 2, 1>), dim3(nblk), dim3(256), lds, s, p);
+  else if (wgrad_taps_cb(p) == 64)
     hipLaunchKernelGGL((k_wgrad_taps<64, 8, 0, 1, 1>), dim3(nblk), dim3(512), lds, s, p);
   else
     hipLaunchKernelGGL((k_wgrad_taps<32, 4, 0, 1, 1>), dim3(nblk), dim3(256), lds, s, p);
@@ -1112,20 +1082,7 @@ __device__ __forceinline__ floatx16 wsp_mfma(uint4 a, uint4 b, floatx16 c) {
                                                  __builtin_bit_cast(wsp_bf8, b), c, 0, 0, 0);
 }
 
-// NS > 2 (X3 only): an NS-slot LDS-DMA ring with hand-counted waits (items
-// it+1 .. it+NS-2 in flight while item it computes; one workgroup per CU).
-template <int CT, bool X4>
-struct WspGeo {
-  static constexpr int KC = CT == 64 ? 64 : 32, PITCH = KC + 4;
-  static constexpr int PSZ = 64 * PITCH, QSZ = CT * PITCH;
-  static constexpr int G = X4 ? 4 : 1;
-  // DMA wave-instructions per item; every wave issues at least DMIN of them
-  static constexpr int NPW = (PSZ / G + 63) / 64, NQW = (QSZ / G + 63) / 64;
-  static constexpr int DMIN = NPW / 4 + NQW / 4;
-  static constexpr int RING = 2 * DMIN < 64 ? 4 : 3;  // vmcnt allowance (NS-2)*DMIN < 64
-};
-
-template <int CT, bool X4, bool X3, int NS = 2>
+template <int CT, bool X4, bool X3>
 __global__ __launch_bounds__(256, 2) void k_wgrad_sp(WgradParams p) {
   constexpr int KC = CT == 64 ? 64 : 32, PITCH = KC + 4;
   static_assert((PITCH / 4) % 2 == 1, "ds_read_b128 conflict-free pitch");
@@ -1134,7 +1091,6 @@ __global__ __launch_bounds__(256, 2) void k_wgrad_sp(WgradParams p) {
   constexpr int G = X4 ? 4 : 1;             // floats per lane per DMA
   constexpr int PN = (PSZ / G + 255) / 256;  // DMA rounds per wave (upper bound)
   constexpr int QN = (QSZ / G + 255) / 256;
-  static_assert(NS == 2 || (X3 && NS <= WspGeo<CT, X4>::RING), "ring only on the x3 path");
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float *Ps0 = smem, *Qs0 = smem + PSZ, *Ps1 = smem + PSZ + QSZ, *Qs1 = Ps1 + PSZ;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -1226,28 +1182,6 @@ __global__ __launch_bounds__(256, 2) void k_wgrad_sp(WgradParams p) {
       }
     }
   };
-  if constexpr (NS > 2) {
-    constexpr int D = WspGeo<CT, X4>::DMIN, SLOT = PSZ + QSZ;
-#pragma unroll
-    for (int k = 0; k < NS - 1; ++k)
-      if (it0 + k < it1) stage(it0 + k, smem + k * SLOT, smem + k * SLOT + PSZ);
-    int sl = 0;
-    for (int it = it0; it < it1; ++it) {
-      const int ahead = min(NS - 2, it1 - 1 - it);  // items staged after this one
-      if (ahead >= 2)
-        asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::"n"(2 * D) : "memory");
-      else if (ahead == 1)
-        asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::"n"(D) : "memory");
-      else
-        asm volatile("s_waitcnt vmcnt(0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-      if (it + NS - 1 < it1) {
-        float *nx = smem + (sl == 0 ? NS - 1 : sl - 1) * SLOT;
-        stage(it + NS - 1, nx, nx + PSZ);
-      }
-      x3_item(smem + sl * SLOT, smem + sl * SLOT + PSZ);
-      sl = sl + 1 == NS ? 0 : sl + 1;
-    }
-  } else {
   if (it0 < it1) stage(it0, Ps0, Qs0);
   __syncthreads();
   for (int it = it0; it < it1; ++it) {
@@ -1290,7 +1224,6 @@ __global__ __launch_bounds__(256, 2) void k_wgrad_sp(WgradParams p) {
     }
     __syncthreads();  // retires this wave's LDS-DMA and publishes the next chunk
   }
-  }
   float *dst = p.slab + (int64_t)split * p.R * p.C;
 #pragma unroll
   for (int t = 0; t < NJ; ++t) {
@@ -1325,20 +1258,10 @@ static hipError_t launch_wgrad_sp(const WgradParams &p, hipStream_t s) {
   const int KC = wgrad_sp_kc(p.CT);
   const size_t lds = sizeof(float) * 2 * (size_t)(64 + p.CT) * (KC + 4);
   const bool x3 = p.bf16 == 3;
-  // x3: STGCN_AB_WSP_RING builds select the LDS-DMA ring (WspGeo::RING slots, one
-  // workgroup per CU): measured 1% SLOWER on cfg2 than the two-buffer schedule
-  // at two workgroups per CU (4356-4375 vs 4403-4415 clips/s in one A/B call);
-  // A/B measurement only
-  constexpr bool ring = STGCN_AB_WSP_RING != 0;
-#define WSP_LAUNCH(CT, X4, X3)                                                              \
-  do {                                                                                      \
-    constexpr int NSR = WspGeo<CT, X4>::RING;                                               \
-    if (X3 && ring)                                                                         \
-      hipLaunchKernelGGL((k_wgrad_sp<CT, X4, X3, X3 ? NSR : 2>), dim3(nblk), dim3(256),     \
-                         sizeof(float) * NSR * (size_t)(64 + CT) * (WspGeo<CT, X4>::KC + 4), s, p); \
-    else                                                                                    \
-      hipLaunchKernelGGL((k_wgrad_sp<CT, X4, X3>), dim3(nblk), dim3(256), lds, s, p);       \
-  } while (0)
+  // (x3: the two-buffer schedule at two workgroups per CU; a deeper LDS-DMA ring at
+  // one per CU measured 1% slower on cfg2, 4356-4375 vs 4403-4415 clips/s)
+#define WSP_LAUNCH(CT, X4, X3) \
+  hipLaunchKernelGGL((k_wgrad_sp<CT, X4, X3>), dim3(nblk), dim3(256), lds, s, p)
   if (p.CT == 64) {
     if (x4)
       { if (x3) WSP_LAUNCH(64, true, true); else WSP_LAUNCH(64, true, false); }
@@ -3379,7 +3302,7 @@ static int bwd3_rows(int V, int K) {
 static bool joint_fast(int V) { return V == 18 || V == 25 || V == 50; }
 
 bool gather_prev_supported(int C, int T, int V) {
-  return STGCN_AB_JOINT3 == 0 && joint_fast(V) && ((int64_t)C * T) % 256 == 0 &&
+  return joint_fast(V) && ((int64_t)C * T) % 256 == 0 &&
          sizeof(float) * ((size_t)2 * 256 * V + (size_t)V * ((V + 3) & ~3)) <= 160 * 1024;
 }
 
@@ -3387,12 +3310,11 @@ hipError_t launch_gather_fwd(const float *x, const float *mean, const float *inv
                              const float *g, const float *b, const float *A, float *G, int N,
                              int C, int T, int V, int K, int relu, hipStream_t s, unsigned *amax,
                              const PrevBn *pv) {
-  constexpr bool joint3 = STGCN_AB_JOINT3 != 0;  // A/B builds only (ab_switches.h)
   const PrevBn pvb = pv ? *pv : PrevBn{};
   if (pv && (K != 1 || !gather_prev_supported(C, T, V) || ((uintptr_t)x & 15) != 0 ||
              ((uintptr_t)G & 15) != 0))
     return hipErrorInvalidValue;  // (x from U: k_gather4 only; checked by the caller first)
-  if (!pv && !joint3 && !amax && K > 1 && (V == 25 || V == 50) && ((uintptr_t)x & 15) == 0 &&
+  if (!pv && !amax && K > 1 && (V == 25 || V == 50) && ((uintptr_t)x & 15) == 0 &&
       ((uintptr_t)G & 15) == 0) {  // partitioned graphs: contraction on MFMA
     const int64_t rows = (int64_t)N * C * T;
     const bool done =
@@ -3403,7 +3325,7 @@ hipError_t launch_gather_fwd(const float *x, const float *mean, const float *inv
     if (done) return hipGetLastError();
   }
   const size_t lds4 = sizeof(float) * ((size_t)2 * 256 * V + (size_t)K * V * ((V + 3) & ~3));
-  if (!joint3 && joint_fast(V) && ((int64_t)C * T) % 256 == 0 && ((uintptr_t)x & 15) == 0 &&
+  if (joint_fast(V) && ((int64_t)C * T) % 256 == 0 && ((uintptr_t)x & 15) == 0 &&
       ((uintptr_t)G & 15) == 0 && lds4 <= 160 * 1024) {
     const int64_t rows = (int64_t)N * C * T;
     const dim3 grid4((unsigned)(rows / 256));
@@ -3506,52 +3428,7 @@ __global__ __launch_bounds__(256) void k_sum_nt4(const float *X, int C, int T, i
   }
 }
 
-// k_sum_nt4 over a bf16 tensor (capi.hip dz_bf16): 4 bf16 = 8 bytes per load,
-// the same period / shift bookkeeping (8-byte boundary below a row's start)
-__global__ __launch_bounds__(256) void k_sum_nt4_bf16(const __bf16 *X, int C, int T, int V,
-                                                      double *out) {
-  __shared__ double part[1024];
-  const int c = blockIdx.x, n = blockIdx.y, tid = threadIdx.x;
-  const int L = T * V;
-  const int per = V / (V % 4 == 0 ? 4 : (V % 2 == 0 ? 2 : 1));
-  const int A = 256 / per * per;
-  const int64_t start = ((int64_t)n * C + c) * L;
-  const int shift = (int)(start & 3);
-  const uint2 *src = reinterpret_cast<const uint2 *>(X + (start - shift));
-  const int nf = (L + shift + 3) / 4;
-  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-  auto f0 = [](unsigned w) { return __builtin_bit_cast(float, w << 16); };
-  auto f1 = [](unsigned w) { return __builtin_bit_cast(float, w & 0xffff0000u); };
-  if (tid < A) {
-    for (int f = tid; f < nf; f += A) {
-      const uint2 q = src[f];
-      const int p0 = 4 * f - shift;
-      if (p0 >= 0 && p0 < L) a0 += f0(q.x);
-      if (p0 + 1 >= 0 && p0 + 1 < L) a1 += f1(q.x);
-      if (p0 + 2 >= 0 && p0 + 2 < L) a2 += f0(q.y);
-      if (p0 + 3 >= 0 && p0 + 3 < L) a3 += f1(q.y);
-    }
-  }
-  part[4 * tid] = a0;
-  part[4 * tid + 1] = a1;
-  part[4 * tid + 2] = a2;
-  part[4 * tid + 3] = a3;
-  __syncthreads();
-  if (tid < V) {
-    double acc = 0.0;
-    for (int q = (tid + shift) % V; q < 4 * A; q += V) acc += part[q];
-    atomicAdd(out + c * V + tid, acc);
-  }
-}
-
-hipError_t launch_sum_nt(const float *X, int N, int C, int T, int V, double *out, hipStream_t s,
-                         int x_bf16) {
-  if (x_bf16) {  // (a bf16 tensor in an fp32-sized, 16-byte aligned buffer)
-    if (V > 256 || ((int64_t)N * C * T * V) % 4 != 0) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_sum_nt4_bf16, dim3(C, N), dim3(256), 0, s,
-                       reinterpret_cast<const __bf16 *>(X), C, T, V, out);
-    return hipGetLastError();
-  }
+hipError_t launch_sum_nt(const float *X, int N, int C, int T, int V, double *out, hipStream_t s) {
   // (rows of any alignment: the float4 kernel reads from the 16-byte boundary
   // below a row's start; X 16-byte aligned and a whole number of float4 in
   // total, so no read passes the tensor's end)
@@ -3683,10 +3560,9 @@ static bool launch_bwd56(const float *H, const float *x, const float *mean, cons
                          int relu, bool bf6, hipStream_t s, const PrevBn &prev, bool dry,
                          float *dA_part = nullptr, int64_t part_cap = 0,
                          int64_t *nparts = nullptr) {
-  constexpr bool joint3 = STGCN_AB_JOINT3 != 0;  // A/B builds only (ab_switches.h)
   const bool aligned = ((int64_t)N * C * T * V) % 4 == 0 && ((uintptr_t)x & 15) == 0 &&
                        ((uintptr_t)H & 15) == 0 && ((uintptr_t)dx & 15) == 0;
-  if (!joint3 && aligned && K <= 3 && K * ((V + 1) / 2) * ((V + 31) / 32) <= 48) {
+  if (aligned && K <= 3 && K * ((V + 1) / 2) * ((V + 31) / 32) <= 48) {
     const int64_t rows = (int64_t)N * C * T;
     bool done = false;
 #define STGCN_BWD5(VV, RR, KK)                                                              \
@@ -3704,7 +3580,7 @@ static bool launch_bwd56(const float *H, const float *x, const float *mean, cons
 #undef STGCN_BWD5
     if (done) return true;
   }
-  if (!joint3 && aligned && V == 50 && K <= 3) {  // two-person graph, 2 or 3 partitions
+  if (aligned && V == 50 && K <= 3) {  // two-person graph, 2 or 3 partitions
     const int64_t rows = (int64_t)N * C * T;
     bool done = false;
 #define STGCN_BWD6(KK, BF)                                                                     \
@@ -3734,9 +3610,8 @@ hipError_t launch_spatial_dx(const float *H, const float *x, const float *mean,
                              const PrevBn *prev, float *dA_part, int64_t part_cap,
                              int64_t *nparts) {
   if (nparts) *nparts = 0;
-  // (STGCN_AB_BWD6_EXACT: the exact-split k_spatial_bwd6 for bf16 blocks too)
-  constexpr bool exact6 = STGCN_AB_BWD6_EXACT != 0;
-  const bool bf6 = bf16ops && !exact6;
+  // (V = 50: bf16 blocks run the two-plane k_spatial_bwd6, the fp32 paths its exact-split form)
+  const bool bf6 = bf16ops != 0;
   const PrevBn pv = prev ? *prev : PrevBn();
   if (launch_bwd56(H, x, mean, invstd, g, b, A, dx, dA, sd, sdn, N, C, T, V, K, write_dx, relu,
                    bf6, s, pv, false, dA_part, part_cap, nparts))

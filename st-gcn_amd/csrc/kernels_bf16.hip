@@ -83,48 +83,46 @@ __device__ __forceinline__ float ld_f32(__amdgpu_buffer_rsrc_t rs, unsigned voff
 }
 
 // ---------------------------------------------------------------------------
-// k_conv_bf16: the ConvGemmParams GEMM (see internal.h) on bf16 MFMA.
+// k_conv_bf16: the one-tap (NQ = 1) ConvGemmParams GEMM (see internal.h) on bf16
+// MFMA: the spatial and residual-projection GEMMs (the 9 / 5 / 4-tap temporal
+// GEMMs run on the one-plane k_conv_x3, kernels_x3.hip conv_b1_supported).
 // Workgroup = 4 waves, tile = 64 rows x FT*V columns (FT = kTileCols / V, the
 // fp32 plan), wave w: rows (w&1)*32..+31, column tiles (w>>1)*4..+3.
-// k-step = one tap q x 16 channels of the chunk (CK channels per chunk):
-//   A fragment: packed weights [q][channel octet][64 rows][8] (one ds_read_b128),
-//   B fragment: the input window [position][CK channels] at position
-//               colpos + q*V (one ds_read_b128; slot pitch CK/8 + 1 is odd,
-//               so any 16 lanes of consecutive positions are conflict-free).
+// k-step = 16 channels of the chunk (CK channels per chunk):
+//   A fragment: packed weights [channel octet][64 rows][8] (one ds_read_b128),
+//   B fragment: the input window [position][CK channels] at position colpos
+//               (one ds_read_b128; slot pitch CK/8 + 1 is odd, so any 16 lanes
+//               of consecutive positions are conflict-free).
 // Staging: the weights (already bf16 in HBM, wpk) move by 16-byte LDS-DMA;
 // the window is loaded as fp32 dwords (consecutive lanes = consecutive
 // positions of one channel: coalesced), converted, and written as 16-byte
 // [position][8 channels] pieces. Two LDS buffers; chunk i+1's loads are in
 // flight under chunk i's MFMAs; one barrier per chunk.
 // ---------------------------------------------------------------------------
-template <int NQ, int CK, int V, int SIN>
+constexpr int kCb1Ck = 16;   // chunk channels
+constexpr int kCb1MinB = 2;  // minimum resident workgroups per CU
+
+template <int V, int SIN>
 struct ConvBf16Geo {
+  static constexpr int CK = kCb1Ck;
   static constexpr int FT = kTileCols / V;
   static constexpr int NCOLS = FT * V;
-  static constexpr int SPAN = (SIN * (FT - 1) + NQ) * V;  // window positions
+  static constexpr int SPAN = (SIN * (FT - 1) + 1) * V;   // window positions
   static constexpr int OCT = CK / 8;                      // channel octets per position
   static constexpr int SLOTS = OCT + 1;                   // 16-byte slots per position (odd)
   static constexpr int IMG = SPAN * SLOTS * 16;           // bytes
-  static constexpr int WCH = NQ * OCT * 1024;             // bytes of one packed weight chunk
+  static constexpr int WCH = OCT * 1024;                  // bytes of one packed weight chunk
   static constexpr int BUF = WCH + IMG;
   static constexpr int NIT = SPAN * OCT;                  // (position, octet) staging items
   static constexpr int IPT = (NIT + 255) / 256;           // items per thread
-  static constexpr int WDMA = NQ * OCT;                   // 1 KiB DMA rows per weight chunk
+  static constexpr int WDMA = OCT;                        // 1 KiB DMA rows per weight chunk
   static_assert(CK % 16 == 0 && (SLOTS & 1), "k-step = 16 channels; odd slot pitch");
 };
 
-#ifndef STGCN_CB1_CK  // chunk channels of the NQ = 1 (spatial / projection) GEMMs
-#define STGCN_CB1_CK 16
-#endif
-#ifndef STGCN_CB1_MINB  // ... and their minimum resident workgroups per CU
-#define STGCN_CB1_MINB 2
-#endif
-
-// IB: the input is stored in bf16 (p.in_bf16; the NQ = 1 GEMM over a bf16 dZ,
-// capi.hip dz_bf16): loaded as zero-extended shorts, packed without conversion
-template <int NQ, int CK, int V, int SIN, bool IB = false>
-__global__ __launch_bounds__(256, NQ == 1 ? STGCN_CB1_MINB : 2) void k_conv_bf16(ConvGemmParams p) {
-  using G = ConvBf16Geo<NQ, CK, V, SIN>;
+template <int V, int SIN>
+__global__ __launch_bounds__(256, kCb1MinB) void k_conv_bf16(ConvGemmParams p) {
+  using G = ConvBf16Geo<V, SIN>;
+  constexpr int CK = G::CK;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   char *lds = reinterpret_cast<char *>(smem);
   const int tid = threadIdx.x, lane = tid & 63;
@@ -170,27 +168,12 @@ __global__ __launch_bounds__(256, NQ == 1 ? STGCN_CB1_MINB : 2) void k_conv_bf16
       make_rsrc(reinterpret_cast<const float *>(wblk), (int64_t)nchunks * G::WCH / 4);
   float st[G::IPT][8];
   auto load_img = [&](int chunk) {
-    if constexpr (IB) {
-      const __bf16 *inb = reinterpret_cast<const __bf16 *>(p.in) + (int64_t)n * p.in_bstride +
-                          (int64_t)chunk * CK * cstride;
-      const __amdgpu_buffer_rsrc_t rs = make_rsrc(
-          reinterpret_cast<const float *>(inb), ((int64_t)(p.C - chunk * CK) * cstride + 1) / 2);
+    const __amdgpu_buffer_rsrc_t rs =
+        make_rsrc(inN + (int64_t)chunk * CK * cstride, (int64_t)(p.C - chunk * CK) * cstride);
 #pragma unroll
-      for (int k = 0; k < G::IPT; ++k)
+    for (int k = 0; k < G::IPT; ++k)
 #pragma unroll
-        for (int j = 0; j < 8; ++j)
-          st[k][j] = __builtin_bit_cast(
-              float, (unsigned)__builtin_amdgcn_raw_buffer_load_b16(
-                         rs, voff[k] == kOOB ? (int)kOOB : (int)((voff[k] >> 1) + j * cstride * 2),
-                         0, 0));
-    } else {
-      const __amdgpu_buffer_rsrc_t rs =
-          make_rsrc(inN + (int64_t)chunk * CK * cstride, (int64_t)(p.C - chunk * CK) * cstride);
-#pragma unroll
-      for (int k = 0; k < G::IPT; ++k)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) st[k][j] = ld_f32(rs, voff[k] + (unsigned)(j * cstride * 4));
-    }
+      for (int j = 0; j < 8; ++j) st[k][j] = ld_f32(rs, voff[k] + (unsigned)(j * cstride * 4));
   };
   auto dma_w = [&](int chunk, char *dst) {
     for (int d = wave; d < G::WDMA; d += 4)
@@ -203,18 +186,10 @@ __global__ __launch_bounds__(256, NQ == 1 ? STGCN_CB1_MINB : 2) void k_conv_bf16
     for (int k = 0; k < G::IPT; ++k)
       if (loff[k] >= 0) {
         uint4 v;
-        if constexpr (IB) {  // already bf16 (zero-extended shorts)
-          const auto u = [&](int j) { return __builtin_bit_cast(unsigned, st[k][j]); };
-          v.x = u(0) | (u(1) << 16);
-          v.y = u(2) | (u(3) << 16);
-          v.z = u(4) | (u(5) << 16);
-          v.w = u(6) | (u(7) << 16);
-        } else {
-          v.x = pk_bf16(st[k][0], st[k][1]);
-          v.y = pk_bf16(st[k][2], st[k][3]);
-          v.z = pk_bf16(st[k][4], st[k][5]);
-          v.w = pk_bf16(st[k][6], st[k][7]);
-        }
+        v.x = pk_bf16(st[k][0], st[k][1]);
+        v.y = pk_bf16(st[k][2], st[k][3]);
+        v.z = pk_bf16(st[k][4], st[k][5]);
+        v.w = pk_bf16(st[k][6], st[k][7]);
         *reinterpret_cast<uint4 *>(dst + loff[k]) = v;
       }
   };
@@ -240,21 +215,18 @@ __global__ __launch_bounds__(256, NQ == 1 ? STGCN_CB1_MINB : 2) void k_conv_bf16
     const char *wa = cur + ao;
     const char *ib = cur + G::WCH;
 #pragma unroll
-    for (int q = 0; q < NQ; ++q)
+    for (int o2 = 0; o2 < G::OCT / 2; ++o2) {
+      const bf16x8 a = *reinterpret_cast<const bf16x8 *>(wa + 2 * o2 * 1024);
 #pragma unroll
-      for (int o2 = 0; o2 < G::OCT / 2; ++o2) {
-        const bf16x8 a = *reinterpret_cast<const bf16x8 *>(wa + (q * G::OCT + 2 * o2) * 1024);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const bf16x8 b = *reinterpret_cast<const bf16x8 *>(
-              ib + bo[j] + (q * V * G::SLOTS + 2 * o2) * 16);
-          acc[j] = mfma_bf16(a, b, acc[j]);
-        }
+      for (int j = 0; j < 4; ++j) {
+        const bf16x8 b = *reinterpret_cast<const bf16x8 *>(ib + bo[j] + 2 * o2 * 16);
+        acc[j] = mfma_bf16(a, b, acc[j]);
       }
+    }
     if (more) write_img(nxt + G::WCH);
   }
   __syncthreads();  // every wave done with the buffers (the epilogue reuses LDS)
-  conv_tile_epilogue<V, G::NCOLS, NQ == 1>(p, acc, n, r0, m0, smem);
+  conv_tile_epilogue<V, G::NCOLS, true>(p, acc, n, r0, m0, smem);
 }
 
 // Packs w[r*w_sr + c*w_sc + q*w_sq] as bf16 into
@@ -281,8 +253,6 @@ __global__ void k_pack_conv_w_bf16(const float *w, __bf16 *wpk, int R, int C, in
   wpk[idx] = (__bf16)v;
 }
 
-static int conv_bf16_ck(int NQ) { return NQ == 1 ? STGCN_CB1_CK : 16; }
-
 bool conv_bf16_supported(const ConvGemmParams &p) {
   // a reduction over fewer than 16 channels (the first block's C_in = 3: the
   // spatial GEMM over K*3 channels, the 1x1 projection) stays on the fp32
@@ -291,64 +261,43 @@ bool conv_bf16_supported(const ConvGemmParams &p) {
   if (p.C < 16) return false;
   if (p.V != 18 && p.V != 25 && p.V != 50) return false;
   if (p.FT != kTileCols / p.V) return false;
-  if (p.s_in == 2) return p.NQ == 9 || p.NQ == 1;
-  return p.s_in == 1 && (p.NQ == 1 || p.NQ == 4 || p.NQ == 5 || p.NQ == 9);
+  return p.NQ == 1 && (p.s_in == 1 || p.s_in == 2);
 }
 
 size_t conv_bf16_lds_bytes(const ConvGemmParams &p) {
-  const int CK = conv_bf16_ck(p.NQ);
-  const int span = (p.s_in * (p.FT - 1) + p.NQ) * p.V;
-  const size_t buf = (size_t)p.NQ * (CK / 8) * 1024 + (size_t)span * (CK / 8 + 1) * 16;
+  constexpr int CK = kCb1Ck;
+  const int span = (p.s_in * (p.FT - 1) + 1) * p.V;
+  const size_t buf = (size_t)(CK / 8) * 1024 + (size_t)span * (CK / 8 + 1) * 16;
   return std::max(2 * buf, (size_t)2048);
 }
 
-template <int NQ, int V, int SIN>
+template <int V, int SIN>
 static bool launch_cb_if(const ConvGemmParams &p, int nblk, size_t lds, hipStream_t s) {
   if (p.V != V || p.s_in != SIN) return false;
-  constexpr int CK = NQ == 1 ? STGCN_CB1_CK : 16;
-  if constexpr (NQ == 1 && SIN == 1) {
-    if (p.in_bf16) {
-      hipLaunchKernelGGL((k_conv_bf16<NQ, CK, V, SIN, true>), dim3(nblk), dim3(256), lds, s, p);
-      return true;
-    }
-  }
-  if (p.in_bf16) return false;
-  hipLaunchKernelGGL((k_conv_bf16<NQ, CK, V, SIN>), dim3(nblk), dim3(256), lds, s, p);
+  hipLaunchKernelGGL((k_conv_bf16<V, SIN>), dim3(nblk), dim3(256), lds, s, p);
   return true;
 }
 
-template <int NQ, int SIN>
+template <int SIN>
 static bool launch_cb_v(const ConvGemmParams &p, int nblk, size_t lds, hipStream_t s) {
-  return launch_cb_if<NQ, 18, SIN>(p, nblk, lds, s) || launch_cb_if<NQ, 25, SIN>(p, nblk, lds, s) ||
-         launch_cb_if<NQ, 50, SIN>(p, nblk, lds, s);
+  return launch_cb_if<18, SIN>(p, nblk, lds, s) || launch_cb_if<25, SIN>(p, nblk, lds, s) ||
+         launch_cb_if<50, SIN>(p, nblk, lds, s);
 }
 
 hipError_t launch_conv_bf16(const ConvGemmParams &p, hipStream_t s) {
-  // (bf16 input: the NQ = 1 stride-1 GEMM only; no bf16 output here)
-  if (!conv_bf16_supported(p) || !p.wpk || p.out_bf16 ||
-      (p.in_bf16 && (p.NQ != 1 || p.s_in != 1)))
-    return hipErrorInvalidValue;
-  const int CK = conv_bf16_ck(p.NQ);
+  // (fp32 tensors in and out: the bf16-stored activations go through k_conv_x3)
+  if (!conv_bf16_supported(p) || !p.wpk || p.in_bf16 || p.out_bf16) return hipErrorInvalidValue;
+  constexpr int CK = kCb1Ck;
   const int nch = (p.C + CK - 1) / CK;
   {
-    const int64_t total = (int64_t)p.n_rtiles * nch * CK * p.NQ * 64;
+    const int64_t total = (int64_t)p.n_rtiles * nch * CK * 64;
     hipLaunchKernelGGL(k_pack_conv_w_bf16, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
-                       s, p.w, reinterpret_cast<__bf16 *>(p.wpk), p.R, p.C, p.NQ, CK, nch, p.w_sr,
+                       s, p.w, reinterpret_cast<__bf16 *>(p.wpk), p.R, p.C, 1, CK, nch, p.w_sr,
                        p.w_sc, p.w_sq, total);
   }
   const int nblk = p.N * p.n_mtiles * p.n_rtiles;
   const size_t lds = conv_bf16_lds_bytes(p);
-  bool done = false;
-  if (p.s_in == 2) {
-    done = p.NQ == 9 ? launch_cb_v<9, 2>(p, nblk, lds, s) : launch_cb_v<1, 2>(p, nblk, lds, s);
-  } else {
-    switch (p.NQ) {
-      case 1: done = launch_cb_v<1, 1>(p, nblk, lds, s); break;
-      case 4: done = launch_cb_v<4, 1>(p, nblk, lds, s); break;
-      case 5: done = launch_cb_v<5, 1>(p, nblk, lds, s); break;
-      case 9: done = launch_cb_v<9, 1>(p, nblk, lds, s); break;
-    }
-  }
+  const bool done = p.s_in == 2 ? launch_cb_v<2>(p, nblk, lds, s) : launch_cb_v<1>(p, nblk, lds, s);
   return done ? hipGetLastError() : hipErrorInvalidValue;
 }
 
@@ -596,7 +545,7 @@ __global__ __launch_bounds__((WgBf16Geo<NQ, V, SIN, FT, CB>::NTH), 1) void k_wgr
   // round, kept in a register as (f << 26 | offset) (~0: pitch pad, pad joint
   // or row past the tensor -> OOB -> 0). An item's whole staging is in flight
   // under the previous item's k-steps; one vmcnt(0) + barrier per item.
-  constexpr bool DMA = BI && NQ == 9 && V % 2 == 0 && !STGCN_AB_WG_REGSTAGE;
+  constexpr bool DMA = BI && NQ == 9 && V % 2 == 0;
   constexpr int PW = G::PPITCH / 2, QW = G::QPITCH / 2, VW = G::Vp / 2;  // dwords
   constexpr int PRN = 64 * PW / 64, QRN = CB * QW / 64;  // wave rounds of 64 dwords
   constexpr int PR = (PRN + G::NW - 1) / G::NW, QR = (QRN + G::NW - 1) / G::NW;
@@ -748,8 +697,7 @@ struct WgRawGeo {
 bool wgrad_raw_ok(const WgradParams &p) {
   return p.NQ == 9 && p.V == 25 && p.s_in == 1 && p.off == -4 && p.FT == 4 && p.p_bf16 &&
          p.q_bf16 && p.M % 2 == 0 && p.T_src % 2 == 0 && (int64_t)p.R * p.M * 25 < (1 << 23) &&
-         (int64_t)p.C * p.T_src * 25 < (1 << 23) && p.n_jtiles * 64 >= p.C &&
-         !STGCN_AB_WG_REGSTAGE;
+         (int64_t)p.C * p.T_src * 25 < (1 << 23) && p.n_jtiles * 64 >= p.C;
 }
 
 __global__ __launch_bounds__(512, 1) void k_wgrad_bf16_raw(WgradParams p) {

@@ -788,9 +788,9 @@ hipError_t launch_sp_fwd_bf16(const float *x, const float *mean, const float *in
                               hipStream_t s, const PrevBn *prev) {
   if (!sp_fwd_bf16_supported(C, V, K, R, relu != 0)) return hipErrorInvalidValue;
   // all output channels per workgroup: the two-person graph, and V = 25 with
-  // K = 3 (STGCN_AB_SPF_NARROW25 build: the 64-row k_sp_fwd_bf16 there, A/B only)
-  constexpr bool narrow25 = STGCN_AB_SPF_NARROW25 != 0;
-  const bool wide = V == 50 || (V == 25 && K == 3 && !narrow25 && (R <= 128 || !relu));
+  // K = 3 (the 64-row k_sp_fwd_bf16 there measured slower, cfg3 5,301 vs 5,835
+  // clips/s; it still serves R > 128 with ReLU)
+  const bool wide = V == 50 || (V == 25 && K == 3 && (R <= 128 || !relu));
   const int nch = (C + 15) / 16;
   const int rows = !wide ? 64 : (R <= 64 ? 64 : (R <= 128 ? 128 : 256));
   const int nrt = (R + rows - 1) / rows;
@@ -887,19 +887,15 @@ hipError_t launch_sp_fwd_bf16(const float *x, const float *mean, const float *in
 // it (vmcnt retires loads in order) and one barrier publishes the item (a
 // fenced __syncthreads would drain the ring). The item's fragments are read
 // first as 16-byte vectors (one LDS wait), then converted and multiplied.
-// PB: dZ is stored in bf16 (capi.hip dz_bf16): staged as bf16 PAIRS by 4-byte
-// LDS-DMA (a row's piece from the even element at or below its start: rows
-// of an odd-length clip row start at odd elements on odd rows), rows of 20
-// dwords (17 used, 80-byte pitch); a fragment = one ds_read_b128 + one
-// ds_read_b32, shifted by 16 bits on odd-start rows, positions past the piece
-// masked to 0 -- the same bf16 operand values as rounding the fp32 dZ at
-// fragment read.
+// Ring depth NS = 4 (155.6 / 118.8 KiB, one workgroup per CU, three items in
+// flight): cfg3 5289 vs 5155-5187, cfg5 2352 vs 2301-2303 clips/s against 2
+// slots (two workgroups per CU, one item of lookahead each) in one A/B call.
 // ---------------------------------------------------------------------------
-template <int TR, bool PB = false>
+template <int TR>
 struct WgGkGeo {
   static constexpr int TC = 256, KC = 32;
-  static constexpr int PITCH = PB ? 20 : KC + 4;            // P pitch (dwords)
-  static constexpr int PUSED = KC / 2 + 1;                  // (PB) pairs staged per row
+  static constexpr int NS = 4;                              // ring slots
+  static constexpr int PITCH = KC + 4;                      // P pitch (dwords)
   static constexpr int PSZ = TR * PITCH;                    // dwords
   static constexpr int QSLOTS = TC * 5;                     // 16-byte slots of the G image
   static constexpr int QBYTES = QSLOTS * 16;
@@ -913,6 +909,7 @@ struct WgGkGeo {
   // item still in flight (a wave issuing more waits slightly more, never less)
   static constexpr int DMIN = PROUNDS + QSLOTS / NTH;
   static_assert(PSZ % NTH == 0, "whole P rounds");
+  static_assert(NS * BUF <= 160 * 1024, "LDS budget");
 };
 
 // s_waitcnt vmcnt(ahead * D) (immediates only), then one unfenced barrier
@@ -927,9 +924,10 @@ __device__ __forceinline__ void gk_ring_wait(int ahead) {
     asm volatile("s_waitcnt vmcnt(0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
-template <int TR, int NS, bool PB>
+template <int TR>
 __global__ __launch_bounds__(512, 1) void k_wgrad_gemm_gk(WgradParams p) {
-  using G = WgGkGeo<TR, PB>;
+  using G = WgGkGeo<TR>;
+  constexpr int NS = G::NS;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   char *lds = reinterpret_cast<char *>(smem);
   const int tid = threadIdx.x, lane = tid & 63;
@@ -969,27 +967,14 @@ __global__ __launch_bounds__(512, 1) void k_wgrad_gemm_gk(WgradParams p) {
     const int mt = rem >> 3, kc = rem & 7;
     const int l0 = mt * FTV + kc * G::KC;
     const int lim = min(min(G::KC, FTV - kc * G::KC), L - l0);  // valid positions of the piece
-    // (PB: a resource over the bf16 tensor, in fp32 units of its bytes; r0 and the
-    // clip stride are even, so pair boundaries are dword boundaries)
     const __amdgpu_buffer_rsrc_t rs_p =
-        PB ? make_rsrc(reinterpret_cast<const float *>(reinterpret_cast<const __bf16 *>(p.P) +
-                                                       (int64_t)n * p.p_bstride + (int64_t)r0 * L),
-                       ((int64_t)prow_lim * L + 1) / 2)
-           : make_rsrc(p.P + (int64_t)n * p.p_bstride + (int64_t)r0 * L, (int64_t)prow_lim * L);
+        make_rsrc(p.P + (int64_t)n * p.p_bstride + (int64_t)r0 * L, (int64_t)prow_lim * L);
 #pragma unroll
     for (int i = 0; i < G::PROUNDS; ++i) {
       const int base = (i * G::NW + wave) * 64;  // wave-uniform
       if (base < G::PSZ) {
-        unsigned voff;
-        if constexpr (PB) {  // pair pcol of the row's piece, from element (row start - sh)
-          const int sh = (prow[i] & 1) & (L & 1);
-          const int e = 2 * pcol[i] - sh;  // first element of the pair, rel. to the piece
-          const bool ok = prow[i] >= 0 && prow[i] < prow_lim && pcol[i] < G::PUSED && e < lim;
-          voff = ok ? (unsigned)(prow[i] * L + l0 + e) * 2u : kOOB;
-        } else {
-          const bool ok = prow[i] >= 0 && prow[i] < prow_lim && pcol[i] < lim;
-          voff = ok ? (unsigned)(prow[i] * L + l0 + pcol[i]) * 4u : kOOB;
-        }
+        const bool ok = prow[i] >= 0 && prow[i] < prow_lim && pcol[i] < lim;
+        const unsigned voff = ok ? (unsigned)(prow[i] * L + l0 + pcol[i]) * 4u : kOOB;
         blds_f32(rs_p, voff, reinterpret_cast<float *>(buf) + base);
       }
     }
@@ -1017,7 +1002,7 @@ __global__ __launch_bounds__(512, 1) void k_wgrad_gemm_gk(WgradParams p) {
     for (int j = 0; j < 2; ++j)
 #pragma unroll
       for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-  static_assert(NS >= 2 && NS <= 4, "ring depth");
+  static_assert(NS >= 2 && NS <= 4, "ring depth (gk_ring_wait counts up to two items ahead)");
 #pragma unroll
   for (int k = 0; k < NS - 1; ++k)
     if (it0 + k < it1) stage(it0 + k, lds + k * G::BUF);
@@ -1030,16 +1015,6 @@ __global__ __launch_bounds__(512, 1) void k_wgrad_gemm_gk(WgradParams p) {
     const char *cur = lds + sl * G::BUF;
     sl = sl + 1 == NS ? 0 : sl + 1;
     const float *pa = reinterpret_cast<const float *>(cur) + (wr * 64 + lo) * G::PITCH + 8 * hi;
-    // (PB: dword 4 hi of the row = its pairs from element 8 hi - sh; sh = 1 on odd
-    // rows of an odd-length clip row; the item's valid positions: lim_b)
-    const unsigned *pab = reinterpret_cast<const unsigned *>(cur) + (wr * 64 + lo) * G::PITCH + 4 * hi;
-    const bool shb = PB && (lo & 1) && (L & 1);  // rows wr*64 + i*32 + lo: parity of lo
-    int lim_b = G::KC;
-    if constexpr (PB) {
-      const int n_it = it / p.n_mtiles, rem_it = it - n_it * p.n_mtiles;
-      const int l0b = (rem_it >> 3) * FTV + (rem_it & 7) * G::KC;
-      lim_b = min(min(G::KC, FTV - (rem_it & 7) * G::KC), L - l0b);
-    }
     const char *qb = cur + G::PBYTES + ((wc * 64 + lo) * 5 + hi) * 16;
     // every fragment of the item first, as 16-byte reads (rows are 16-byte
     // aligned: PITCH * 4 = 144 B), one LDS wait, then the conversions and the
@@ -1048,23 +1023,15 @@ __global__ __launch_bounds__(512, 1) void k_wgrad_gemm_gk(WgradParams p) {
     constexpr int NKS = G::KC / 16;
     typedef float f32x4v __attribute__((ext_vector_type(4)));
     f32x4v pf[NKS][2][2];
-    uint4 pq[NKS][2];
-    unsigned pe[NKS][2];
     bf16x8f b[NKS][2];
 #pragma unroll
     for (int s = 0; s < NKS; ++s)
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
-        if constexpr (PB) {
-          const unsigned *src = pab + i * 32 * G::PITCH + 8 * s;
-          pq[s][i] = *reinterpret_cast<const uint4 *>(__builtin_assume_aligned(src, 16));
-          pe[s][i] = src[4];
-        } else {
-          const f32x4v *src = reinterpret_cast<const f32x4v *>(
-              __builtin_assume_aligned(pa + i * 32 * G::PITCH + 16 * s, 16));
-          pf[s][i][0] = src[0];
-          pf[s][i][1] = src[1];
-        }
+        const f32x4v *src = reinterpret_cast<const f32x4v *>(
+            __builtin_assume_aligned(pa + i * 32 * G::PITCH + 16 * s, 16));
+        pf[s][i][0] = src[0];
+        pf[s][i][1] = src[1];
       }
 #pragma unroll
     for (int s = 0; s < NKS; ++s)
@@ -1076,34 +1043,9 @@ __global__ __launch_bounds__(512, 1) void k_wgrad_gemm_gk(WgradParams p) {
       bf16x8f a[2];
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
-        if constexpr (PB) {
-          const uint4 q = pq[s][i];
-          uint4 w = q;
-          if (shb) {  // odd-start row: elements from the high half of dword 0
-            w.x = __builtin_amdgcn_alignbit(q.y, q.x, 16);
-            w.y = __builtin_amdgcn_alignbit(q.z, q.y, 16);
-            w.z = __builtin_amdgcn_alignbit(q.w, q.z, 16);
-            w.w = __builtin_amdgcn_alignbit(pe[s][i], q.w, 16);
-          }
-          // positions k = 16 s + 8 hi + j past the piece (lim_b) are 0 (the pair
-          // at the boundary and, on shifted rows, the element after it)
-          const int k0 = 16 * s + 8 * hi;
-          if (k0 + 8 > lim_b) {
-            unsigned m[4];
-#pragma unroll
-            for (int d = 0; d < 4; ++d)
-              m[d] = (k0 + 2 * d < lim_b ? 0xffffu : 0u) | (k0 + 2 * d + 1 < lim_b ? 0xffff0000u : 0u);
-            w.x &= m[0];
-            w.y &= m[1];
-            w.z &= m[2];
-            w.w &= m[3];
-          }
-          a[i] = __builtin_bit_cast(bf16x8f, w);
-        } else {
-          const f32x4v lo4 = pf[s][i][0], hi4 = pf[s][i][1];
-          a[i] = bf16x8f{(__bf16)lo4.x, (__bf16)lo4.y, (__bf16)lo4.z, (__bf16)lo4.w,
-                         (__bf16)hi4.x, (__bf16)hi4.y, (__bf16)hi4.z, (__bf16)hi4.w};
-        }
+        const f32x4v lo4 = pf[s][i][0], hi4 = pf[s][i][1];
+        a[i] = bf16x8f{(__bf16)lo4.x, (__bf16)lo4.y, (__bf16)lo4.z, (__bf16)lo4.w,
+                       (__bf16)hi4.x, (__bf16)hi4.y, (__bf16)hi4.z, (__bf16)hi4.w};
       }
 #pragma unroll
       for (int i = 0; i < 2; ++i)
@@ -1139,23 +1081,10 @@ void plan_wgrad_gk(WgradParams &w, int T) {
 
 hipError_t launch_wgrad_gk(const WgradParams &p, hipStream_t s) {
   const int nblk = p.n_rtiles * p.n_jtiles * p.S;
-  // ring depth 4 (155.6 / 118.8 KiB, one workgroup per CU, three items in
-  // flight): cfg3 5289 vs 5155-5187, cfg5 2352 vs 2301-2303 clips/s against 2
-  // slots (two workgroups per CU, one item of lookahead each) in one A/B call.
-  // (Before the fragment reads were 16-byte vectors the loop was LDS-latency
-  // bound and 2 slots won: 5141 vs 5063.) STGCN_AB_GK_SLOTS2 builds: A/B only.
-  constexpr bool two = STGCN_AB_GK_SLOTS2 != 0;
-  static_assert(4 * WgGkGeo<128>::BUF <= 160 * 1024, "LDS budget");
-#define GK_LAUNCH(TR, NS, PB)                                                                \
-  hipLaunchKernelGGL((k_wgrad_gemm_gk<TR, NS, PB>), dim3(nblk), dim3((WgGkGeo<TR, PB>::NTH)), \
-                     (NS * WgGkGeo<TR, PB>::BUF), s, p)
-  if (p.p_bf16) {  // bf16 dZ (capi.hip dz_bf16)
-    if (p.CT == 128) GK_LAUNCH(128, 4, true); else GK_LAUNCH(64, 4, true);
-  } else if (p.CT == 128) {
-    if (two) GK_LAUNCH(128, 2, false); else GK_LAUNCH(128, 4, false);
-  } else {
-    if (two) GK_LAUNCH(64, 2, false); else GK_LAUNCH(64, 4, false);
-  }
+#define GK_LAUNCH(TR)                                                                 \
+  hipLaunchKernelGGL((k_wgrad_gemm_gk<TR>), dim3(nblk), dim3((WgGkGeo<TR>::NTH)),     \
+                     (WgGkGeo<TR>::NS * WgGkGeo<TR>::BUF), s, p)
+  if (p.CT == 128) GK_LAUNCH(128); else GK_LAUNCH(64);
 #undef GK_LAUNCH
   return hipGetLastError();
 }

@@ -103,56 +103,19 @@ __device__ __forceinline__ void spb_barrier() {
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
-
-// (a, b) -> packed bf16 planes h, m, l (a == h + m + l exactly; kernels_x3.hip)
-__device__ __forceinline__ void spb_split3(float a, float b, unsigned &h, unsigned &m,
-                                           unsigned &l) {
-  h = spb_pk(a, b);
-  const float ra = a - __builtin_bit_cast(float, h << 16);
-  const float rb = b - __builtin_bit_cast(float, h & 0xffff0000u);
-  m = spb_pk(ra, rb);
-  l = spb_pk(ra - __builtin_bit_cast(float, m << 16), rb - __builtin_bit_cast(float, m & 0xffff0000u));
-}
-// 8 floats -> operand planes (2: h, m; 3: h, m, l)
-template <int NP>
-__device__ __forceinline__ void spb_planes(const float (&v)[8], uint4 (&o)[NP]) {
-  static_assert(NP == 2 || NP == 3, "planes");
-  if constexpr (NP == 2) {
-    spb_split(v[0], v[1], o[0].x, o[1].x);
-    spb_split(v[2], v[3], o[0].y, o[1].y);
-    spb_split(v[4], v[5], o[0].z, o[1].z);
-    spb_split(v[6], v[7], o[0].w, o[1].w);
-  } else {
-    spb_split3(v[0], v[1], o[0].x, o[1].x, o[2].x);
-    spb_split3(v[2], v[3], o[0].y, o[1].y, o[2].y);
-    spb_split3(v[4], v[5], o[0].z, o[1].z, o[2].z);
-    spb_split3(v[6], v[7], o[0].w, o[1].w, o[2].w);
-  }
-}
-// sum over the split products of weight >= 2^-16 of two 3-plane operands:
-// h*h into acc[0], h*m + m*h + h*l + m*m + l*h into acc[1] (kernels_x3.hip)
-__device__ __forceinline__ void spb_mfma6(const uint4 (&a)[3], const uint4 (&b)[3],
-                                          floatx16 (&acc)[2]) {
-  acc[0] = spb_mfma(a[0], b[0], acc[0]);
-  acc[1] = spb_mfma(a[0], b[1], acc[1]);
-  acc[1] = spb_mfma(a[1], b[0], acc[1]);
-  acc[1] = spb_mfma(a[0], b[2], acc[1]);
-  acc[1] = spb_mfma(a[1], b[1], acc[1]);
-  acc[1] = spb_mfma(a[2], b[0], acc[1]);
+// 8 floats -> the two operand planes h, m
+__device__ __forceinline__ void spb_planes(const float (&v)[8], uint4 (&o)[2]) {
+  spb_split(v[0], v[1], o[0].x, o[1].x);
+  spb_split(v[2], v[3], o[0].y, o[1].y);
+  spb_split(v[4], v[5], o[0].z, o[1].z);
+  spb_split(v[6], v[7], o[0].w, o[1].w);
 }
 
-// X3 = false: the bf16 path (bf16 W', dZ rounded to bf16; H, A to 2^-16).
-// X3 = true : the fp32 path of STGCN_F_F32X3 (every operand as its exact 3-way
-//             bf16 split, six products per fp32 product, h*h accumulated apart).
-// DZB: dZ is stored in bf16 (capi.hip dz_bf16; the values the fp32 path rounds
-//      it to): half-size ring slots, so the ring is 6 chunks deep instead of 4.
-template <int V, int K, bool X3, bool DZB = false>
+// The bf16 path: bf16 W', fp32 dZ rounded to bf16; H and A to 2^-16 (two planes).
+template <int V, int K>
 struct SpBwdGeo {
   static_assert(V <= 32, "one 32-joint tile");
-  static constexpr int NPLW = X3 ? 3 : 1;           // W' planes
-  static constexpr int NPLA = X3 ? 3 : 2;           // A planes (dx A operand)
-  static constexpr int NPLX = X3 ? 3 : 1;           // f(BN1(x)) planes (dA B operand)
-  static constexpr int NACC = X3 ? 2 : 1;           // accumulators per tile (h*h apart)
+  static constexpr int NPLA = 2;                    // A planes (dx A operand)
   static constexpr int FT = 8;                      // frames per item (wave = frame)
   static constexpr int NPOS = FT * V;               // positions per item
   // 16-byte pieces per row: NPOS positions from a 16-byte aligned start up to 3
@@ -160,17 +123,12 @@ struct SpBwdGeo {
   static constexpr int NPC = (NPOS + 3 + 3) / 4;
   static constexpr int CB = 32;                     // input channels per item
   static constexpr int CR = 16;                     // dZ channels per chunk (one k-step)
-  static constexpr int D = DZB ? 6 : 4;             // ring depth (chunks)
+  static constexpr int D = 4;                       // ring depth (chunks)
   // row pitch (floats): whole pieces, and 8 rows apart = 32 banks apart
   static constexpr int RP = (NPC * 4) % 8 == 0 ? NPC * 4 + 4 : NPC * 4;
-  static_assert(NPOS % 8 == 0, "item starts p0 16-byte aligned within a row (fp32 and bf16)");
-  // the dZ ring rows: fp32 as the x slice, or bf16 (NPCZ 8-element pieces from
-  // the 16-byte boundary below the row start; pitch = 8 mod 16 elements)
-  static constexpr int NPCZ = DZB ? (NPOS + 7 + 7) / 8 : NPC;
-  static constexpr int RPZ = DZB ? ((NPCZ * 8) % 16 == 0 ? NPCZ * 8 + 8 : NPCZ * 8) : RP;
-  static constexpr int ZSZ = DZB ? 2 : 4;
-  static constexpr int RING_SLOT = CR * RPZ * ZSZ;  // [r][RPZ]
-  static constexpr int W_BYTES = K * NPLW * CR * 64;  // W' chunk [k][plane][octet 2][ci 32][8]
+  static_assert(NPOS % 4 == 0, "item starts p0 16-byte aligned within a row");
+  static constexpr int RING_SLOT = CR * RP * 4;     // the dZ ring rows [r][RP], as the x slice
+  static constexpr int W_BYTES = K * CR * 64;       // W' chunk [k][octet 2][ci 32][8]
   static constexpr int WPW = W_BYTES / 16 / 8;      // W' pieces per wave
   static constexpr int XBP = 80;                    // f(BN1(x)) image row pitch, bytes
   static constexpr int XB_ROWS = NPOS + 1;          // rows (frame, w) + one zero row
@@ -184,18 +142,18 @@ struct SpBwdGeo {
   static constexpr int OFF_ST = OFF_X + CB * RP * 4;                        // fp32 [ci][SP]
   static constexpr int OFF_XB = (OFF_ST + CB * SP * 4 + 15) & ~15;          // bf16 image
   // [mean|invstd|a|beta][CMAX] of BN1, then (prev mode) the same of the previous block's BN2
-  static constexpr int OFF_TAB = (OFF_XB + NPLX * XB_PLANE + 15) & ~15;
+  static constexpr int OFF_TAB = (OFF_XB + XB_PLANE + 15) & ~15;
   static constexpr int OFF_SUM = OFF_TAB + 8 * CMAX * 4;  // [s | sn | s1 | s2][CMAX] fp64
   static constexpr int LDS = OFF_SUM + 4 * CMAX * 8;
   static_assert(LDS <= 160 * 1024, "LDS budget");
   static_assert(K * V * V * 4 <= D * RING_SLOT, "dA reduction fits the ring");
   static_assert(W_BYTES % 128 == 0 && WPW <= 64, "W' pieces per wave");
-  static_assert(NPC <= 64 && NPCZ <= 64, "one DMA instruction per row");
+  static_assert(NPC <= 64, "one DMA instruction per row");
 };
 
 struct SpBwdParams {
   const float *dZ, *x, *mean, *invstd, *g, *b;
-  const __bf16 *wpk;   // [cb][chunk][k][plane][octet][ci 32][8]
+  const __bf16 *wpk;   // [cb][chunk][k][octet][ci 32][8]
   const __bf16 *aimg;  // [k][ks][plane][lane][8]
   float *dx, *dA;
   double *sd, *sdn;
@@ -203,10 +161,10 @@ struct SpBwdParams {
   PrevBn prev;  // prev mode (internal.h): x is the previous block's U
 };
 
-template <int V, int K, bool X3, bool DZB>
+template <int V, int K>
 __global__ __launch_bounds__(512, 1) void k_sp_bwd_fused(SpBwdParams P) {
-  using G = SpBwdGeo<V, K, X3, DZB>;
-  constexpr int D = G::D, NACC = G::NACC;
+  using G = SpBwdGeo<V, K>;
+  constexpr int D = G::D;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   char *lds = reinterpret_cast<char *>(smem);
   const int tid = threadIdx.x, lane = tid & 63;
@@ -240,10 +198,8 @@ __global__ __launch_bounds__(512, 1) void k_sp_bwd_fused(SpBwdParams P) {
     sums[2 * G::CMAX + c] = 0.0;
     sums[3 * G::CMAX + c] = 0.0;
   }
-  for (int e = tid; e < G::NPLX * (G::XBP / 4); e += 512) {
-    const int p = e / (G::XBP / 4), q = e - p * (G::XBP / 4);
-    reinterpret_cast<unsigned *>(lds + G::OFF_XB + p * G::XB_PLANE + G::NPOS * G::XBP)[q] = 0u;
-  }
+  for (int e = tid; e < G::XBP / 4; e += 512)
+    reinterpret_cast<unsigned *>(lds + G::OFF_XB + G::NPOS * G::XBP)[e] = 0u;
   __syncthreads();  // (full drain: the table loads are ordinary loads)
   {
     const spb_i4 ra = spb_rsrc(P.aimg, G::AIMG_BYTES);
@@ -271,9 +227,7 @@ __global__ __launch_bounds__(512, 1) void k_sp_bwd_fused(SpBwdParams P) {
   auto start_item = [&]() {
     int n = 0, ft = 0, cb = 0;
     if (ik < myitems) decode(first + ik * NG, n, ft, cb);
-    rz = DZB ? spb_rsrc(reinterpret_cast<const __bf16 *>(P.dZ) + (int64_t)n * P.R * TV,
-                        (int64_t)P.R * TV * 2)
-             : spb_rsrc(P.dZ + (int64_t)n * P.R * TV, (int64_t)P.R * TV * 4);
+    rz = spb_rsrc(P.dZ + (int64_t)n * P.R * TV, (int64_t)P.R * TV * 4);
     irow = ft * G::FT * V;
     iwb = cb * NCH * G::W_BYTES;
   };
@@ -285,10 +239,9 @@ __global__ __launch_bounds__(512, 1) void k_sp_bwd_fused(SpBwdParams P) {
     for (int h = 0; h < 2; ++h) {
       const int r = 2 * wave + h;
       const int start = irow + r * TV;  // from the 16-byte boundary below: the row's shift
-      constexpr int EPP = 16 / G::ZSZ;  // elements per 16-byte piece
-      const unsigned voff = (unsigned)(((start & ~(EPP - 1)) + EPP * lane) * G::ZSZ);
-      if (lane < G::NPCZ)
-        spb_dma16(rz, voff, lds0 + G::OFF_RING + islot * G::RING_SLOT + r * G::RPZ * G::ZSZ);
+      const unsigned voff = (unsigned)(((start & ~3) + 4 * lane) * 4);
+      if (lane < G::NPC)
+        spb_dma16(rz, voff, lds0 + G::OFF_RING + islot * G::RING_SLOT + r * G::RP * 4);
     }
     if (lane < G::WPW)
       spb_dma16(rw, (unsigned)(iwb + ic * G::W_BYTES + wave * G::WPW * 16 + lane * 16),
@@ -316,13 +269,11 @@ __global__ __launch_bounds__(512, 1) void k_sp_bwd_fused(SpBwdParams P) {
     }
   };
 
-  floatx16 T[K][NACC], S[K][NACC], dacc[K][NACC];
+  floatx16 T[K], S[K], dacc[K];
 #pragma unroll
   for (int k = 0; k < K; ++k)
 #pragma unroll
-    for (int a = 0; a < NACC; ++a)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) dacc[k][a][i] = 0.f;
+    for (int i = 0; i < 16; ++i) dacc[k][i] = 0.f;
   float *st = reinterpret_cast<float *>(lds + G::OFF_ST);
   const float *xs = reinterpret_cast<const float *>(lds + G::OFF_X);
 
@@ -338,9 +289,7 @@ __global__ __launch_bounds__(512, 1) void k_sp_bwd_fused(SpBwdParams P) {
 #pragma unroll
     for (int kk = 0; kk < K; ++kk)
 #pragma unroll
-      for (int a = 0; a < NACC; ++a)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) T[kk][a][i] = S[kk][a][i] = 0.f;
+      for (int i = 0; i < 16; ++i) T[kk][i] = S[kk][i] = 0.f;
 
     // ---- H_k = W_k^T dZ in both orientations, 16 channels of dZ per chunk
     for (int c = 0; c < NCH; ++c, ++gch) {
@@ -357,64 +306,32 @@ __global__ __launch_bounds__(512, 1) void k_sp_bwd_fused(SpBwdParams P) {
       // 8 hi + j starts (8 hi + j) * TV mod 4 = j * TV mod 4 floats into its LDS row
       const char *wb = lds + G::OFF_W + slot * G::W_BYTES + hi * 512 + lo * 16;
       float dv[8];
-      uint4 a;  // dZ rounded to bf16 (the X3 path splits dv instead)
-      if constexpr (DZB) {  // stored in bf16: the same values, read as shorts
-        const unsigned short *rz =
-            reinterpret_cast<const unsigned short *>(lds + G::OFF_RING + slot * G::RING_SLOT) +
-            8 * hi * G::RPZ + f * V + (lo < V ? lo : V - 1);
-        unsigned hv[8];
+      uint4 a;  // dZ rounded to bf16
+      const float *rz = reinterpret_cast<const float *>(lds + G::OFF_RING + slot * G::RING_SLOT) +
+                        8 * hi * G::RP + f * V + (lo < V ? lo : V - 1);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) hv[j] = rz[j * G::RPZ + ((j * TV) & 7)];
+      for (int j = 0; j < 8; ++j) dv[j] = rz[j * G::RP + ((j * TV) & 3)];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) hv[j] = lo < V ? hv[j] : 0u;
-        a.x = hv[0] | (hv[1] << 16);
-        a.y = hv[2] | (hv[3] << 16);
-        a.z = hv[4] | (hv[5] << 16);
-        a.w = hv[6] | (hv[7] << 16);
-      } else {
-        const float *rz =
-            reinterpret_cast<const float *>(lds + G::OFF_RING + slot * G::RING_SLOT) +
-            8 * hi * G::RPZ + f * V + (lo < V ? lo : V - 1);
+      for (int j = 0; j < 8; ++j) dv[j] = lo < V ? dv[j] : 0.f;
+      a.x = spb_pk(dv[0], dv[1]);
+      a.y = spb_pk(dv[2], dv[3]);
+      a.z = spb_pk(dv[4], dv[5]);
+      a.w = spb_pk(dv[6], dv[7]);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) dv[j] = rz[j * G::RPZ + ((j * TV) & 3)];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) dv[j] = lo < V ? dv[j] : 0.f;
-        a.x = spb_pk(dv[0], dv[1]);
-        a.y = spb_pk(dv[2], dv[3]);
-        a.z = spb_pk(dv[4], dv[5]);
-        a.w = spb_pk(dv[6], dv[7]);
-      }
-      if constexpr (!X3) {
-#pragma unroll
-        for (int kk = 0; kk < K; ++kk) {
-          const uint4 w = *reinterpret_cast<const uint4 *>(wb + kk * 1024);
-          T[kk][0] = spb_mfma(a, w, T[kk][0]);  // [v][ci] = sum_r dZ[r][v] W_k[r][ci]
-          S[kk][0] = spb_mfma(w, a, S[kk][0]);  // [ci][v]
-        }
-      } else {
-        uint4 a[3];
-        spb_planes<3>(dv, a);
-#pragma unroll
-        for (int kk = 0; kk < K; ++kk) {
-          uint4 w[3];
-#pragma unroll
-          for (int p = 0; p < 3; ++p)
-            w[p] = *reinterpret_cast<const uint4 *>(wb + (kk * 3 + p) * 1024);
-          spb_mfma6(a, w, T[kk]);
-          spb_mfma6(w, a, S[kk]);
-        }
+      for (int kk = 0; kk < K; ++kk) {
+        const uint4 w = *reinterpret_cast<const uint4 *>(wb + kk * 1024);
+        T[kk] = spb_mfma(a, w, T[kk]);  // [v][ci] = sum_r dZ[r][v] W_k[r][ci]
+        S[kk] = spb_mfma(w, a, S[kk]);  // [ci][v]
       }
     }
 
     // ---- dx^T[w][ci] = sum_k sum_v A_k[v][w] H_k^T[v][ci] -> dx row image [ci][f*V + w]
     {
-      floatx16 dxp[K][NACC];  // one chain per partition, summed at the end
+      floatx16 dxp[K];  // one chain per partition, summed at the end
 #pragma unroll
       for (int kk = 0; kk < K; ++kk)
 #pragma unroll
-        for (int a = 0; a < NACC; ++a)
-#pragma unroll
-          for (int i = 0; i < 16; ++i) dxp[kk][a][i] = 0.f;
+        for (int i = 0; i < 16; ++i) dxp[kk][i] = 0.f;
       const char *aim = lds + G::OFF_A + lane * 16;
 #pragma unroll
       for (int kk = 0; kk < K; ++kk)
@@ -422,28 +339,19 @@ __global__ __launch_bounds__(512, 1) void k_sp_bwd_fused(SpBwdParams P) {
         for (int ks = 0; ks < 2; ++ks) {
           float tv[8];
 #pragma unroll
-          for (int j = 0; j < 8; ++j)
-            tv[j] = NACC == 2 ? T[kk][0][8 * ks + j] + T[kk][NACC - 1][8 * ks + j]
-                              : T[kk][0][8 * ks + j];
+          for (int j = 0; j < 8; ++j) tv[j] = T[kk][8 * ks + j];
           uint4 b[G::NPLA], am[G::NPLA];
-          spb_planes<G::NPLA>(tv, b);
+          spb_planes(tv, b);
 #pragma unroll
           for (int p = 0; p < G::NPLA; ++p)
             am[p] = *reinterpret_cast<const uint4 *>(aim + ((kk * 2 + ks) * G::NPLA + p) * 1024);
-          if constexpr (!X3) {
-            dxp[kk][0] = spb_mfma(am[0], b[0], dxp[kk][0]);
-            dxp[kk][0] = spb_mfma(am[1], b[0], dxp[kk][0]);
-            dxp[kk][0] = spb_mfma(am[0], b[1], dxp[kk][0]);
-          } else {
-            spb_mfma6(am, b, dxp[kk]);
-          }
+          dxp[kk] = spb_mfma(am[0], b[0], dxp[kk]);
+          dxp[kk] = spb_mfma(am[1], b[0], dxp[kk]);
+          dxp[kk] = spb_mfma(am[0], b[1], dxp[kk]);
         }
-      floatx16 dxa = dxp[0][0];
+      floatx16 dxa = dxp[0];
 #pragma unroll
-      for (int kk = 0; kk < K; ++kk)
-#pragma unroll
-        for (int a = 0; a < NACC; ++a)
-          if (kk || a) dxa += dxp[kk][a];
+      for (int kk = 1; kk < K; ++kk) dxa += dxp[kk];
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
         const int w = (i & 3) + 8 * (i >> 2) + 4 * hi;
@@ -453,7 +361,7 @@ __global__ __launch_bounds__(512, 1) void k_sp_bwd_fused(SpBwdParams P) {
     spb_barrier();  // dx row image complete (the x slice landed with the item's chunk waits)
 
     // ---- row pass, 16 threads per channel: ReLU mask, BN1 sums, dx store, and
-    // f(BN1(x)) into the dA operand image (row (frame, w), slot of ci; bf16 planes)
+    // f(BN1(x)) into the dA operand image (row (frame, w), slot of ci; bf16)
     {
       const int ci = tid >> 4, part = tid & 15;
       const int c = cb * G::CB + ci;
@@ -505,14 +413,7 @@ __global__ __launch_bounds__(512, 1) void k_sp_bwd_fused(SpBwdParams P) {
         if (pos < G::NPOS) {
           const float fx = live ? (P.relu ? fmaxf(bn, 0.f) : bn) : 0.f;
           __bf16 *xr = xbi + pos * (G::XBP / 2);  // row (frame, w) = pos
-          const __bf16 h = (__bf16)fx;
-          xr[0] = h;
-          if constexpr (X3) {
-            const float r1 = fx - (float)h;
-            const __bf16 m = (__bf16)r1;
-            xr[G::XB_PLANE / 2] = m;
-            xr[G::XB_PLANE] = (__bf16)(r1 - (float)m);
-          }
+          xr[0] = (__bf16)fx;
         }
       }
       double ds = s, dn = sn, d1 = s1, d2 = s2;
@@ -543,27 +444,16 @@ __global__ __launch_bounds__(512, 1) void k_sp_bwd_fused(SpBwdParams P) {
       const char *xb = lds + G::OFF_XB + row * G::XBP + hi * 16;
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
-        uint4 xv[G::NPLX];
-#pragma unroll
-        for (int p = 0; p < G::NPLX; ++p)
-          xv[p] = *reinterpret_cast<const uint4 *>(xb + p * G::XB_PLANE + ks * 32);
+        const uint4 xv = *reinterpret_cast<const uint4 *>(xb + ks * 32);
 #pragma unroll
         for (int kk = 0; kk < K; ++kk) {
           float sv[8];
 #pragma unroll
-          for (int j = 0; j < 8; ++j)
-            sv[j] = NACC == 2 ? S[kk][0][8 * ks + j] + S[kk][NACC - 1][8 * ks + j]
-                              : S[kk][0][8 * ks + j];
-          if constexpr (!X3) {
-            uint4 sp[2];
-            spb_planes<2>(sv, sp);
-            dacc[kk][0] = spb_mfma(sp[0], xv[0], dacc[kk][0]);
-            dacc[kk][0] = spb_mfma(sp[1], xv[0], dacc[kk][0]);
-          } else {
-            uint4 sp[3];
-            spb_planes<3>(sv, sp);
-            spb_mfma6(sp, xv, dacc[kk]);
-          }
+          for (int j = 0; j < 8; ++j) sv[j] = S[kk][8 * ks + j];
+          uint4 sp[2];
+          spb_planes(sv, sp);
+          dacc[kk] = spb_mfma(sp[0], xv, dacc[kk]);
+          dacc[kk] = spb_mfma(sp[1], xv, dacc[kk]);
         }
       }
     }
@@ -581,8 +471,7 @@ __global__ __launch_bounds__(512, 1) void k_sp_bwd_fused(SpBwdParams P) {
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
       const int v = (i & 3) + 8 * (i >> 2) + 4 * hi;
-      const float val = NACC == 2 ? dacc[kk][0][i] + dacc[kk][NACC - 1][i] : dacc[kk][0][i];
-      if (v < V && lo < V) atomicAdd(dred + (kk * V + v) * V + lo, val);
+      if (v < V && lo < V) atomicAdd(dred + (kk * V + v) * V + lo, dacc[kk][i]);
     }
   __syncthreads();
   if (myitems > 0) {
@@ -598,10 +487,9 @@ __global__ __launch_bounds__(512, 1) void k_sp_bwd_fused(SpBwdParams P) {
   }
 }
 
-// W (K*R, C) -> [cb][chunk][k][plane][octet][ci 32][8] bf16 (16 channels of R per
-// chunk; planes: bf16 rounding (NP = 1) or the exact h, m, l split (NP = 3))
-__global__ void k_pack_spb_w(const float *W, __bf16 *wpk, int K, int R, int C, int NP) {
-  const int64_t total = (int64_t)K * R * C * NP;
+// W (K*R, C) -> [cb][chunk][k][octet][ci 32][8] bf16 (16 channels of R per chunk)
+__global__ void k_pack_spb_w(const float *W, __bf16 *wpk, int K, int R, int C) {
+  const int64_t total = (int64_t)K * R * C;
   const int nch = R / 16;
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total;
        e += (int64_t)gridDim.x * blockDim.x) {
@@ -612,42 +500,34 @@ __global__ void k_pack_spb_w(const float *W, __bf16 *wpk, int K, int R, int C, i
     r /= 32;
     const int o = (int)(r % 2);
     r /= 2;
-    const int p = (int)(r % NP);
-    r /= NP;
     const int k = (int)(r % K);
     r /= K;
     const int c = (int)(r % nch);
     const int cb = (int)(r / nch);
     const int rr = c * 16 + 8 * o + jj;
-    const float w = W[((int64_t)k * R + rr) * C + cb * 32 + ci];
-    const __bf16 h = (__bf16)w;
-    const float r1 = w - (float)h;
-    const __bf16 m = (__bf16)r1;
-    wpk[e] = p == 0 ? h : (p == 1 ? m : (__bf16)(r1 - (float)m));
+    wpk[e] = (__bf16)W[((int64_t)k * R + rr) * C + cb * 32 + ci];
   }
 }
 
-// A (K, V, V) -> the dx A-operand image [k][ks][plane h, m(, l)][lane][8]:
+// A (K, V, V) -> the dx A-operand image [k][ks][plane h, m][lane][8]:
 // lane (lo, hi), j -> A_k[v = 16 ks + (j & 3) + 8 (j >> 2) + 4 hi][w = lo]
-__global__ void k_pack_spb_a(const float *A, __bf16 *img, int K, int V, int NP) {
-  const int total = K * 2 * NP * 512;
+__global__ void k_pack_spb_a(const float *A, __bf16 *img, int K, int V) {
+  const int total = K * 2 * 2 * 512;
   for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += gridDim.x * blockDim.x) {
     int r = e;
     const int j = r % 8;
     r /= 8;
     const int lane = r % 64;
     r /= 64;
-    const int plane = r % NP;
-    r /= NP;
+    const int plane = r % 2;
+    r /= 2;
     const int ks = r % 2;
     const int k = r / 2;
     const int lo = lane & 31, hi = lane >> 5;
     const int v = 16 * ks + (j & 3) + 8 * (j >> 2) + 4 * hi, w = lo;
     const float a = (v < V && w < V) ? A[((int64_t)k * V + v) * V + w] : 0.f;
     const __bf16 h = (__bf16)a;
-    const float r1 = a - (float)h;
-    const __bf16 m = (__bf16)r1;
-    img[e] = plane == 0 ? h : (plane == 1 ? m : (__bf16)(r1 - (float)m));
+    img[e] = plane == 0 ? h : (__bf16)(a - (float)h);
   }
 }
 
@@ -928,7 +808,7 @@ __global__ __launch_bounds__(512, 1) void k_sp50_dx(Sp50Params P) {
 #pragma unroll
           for (int j = 0; j < 8; ++j) tv[j] = T[kk][vt][8 * ks + j];
           uint4 bpl[2];
-          spb_planes<2>(tv, bpl);
+          spb_planes(tv, bpl);
           const int fr = (((kk * 2 + wt) * 2 + vt) * 2 + ks) * 2;
           const uint4 am0 = *reinterpret_cast<const uint4 *>(aim + fr * 1024);
           const uint4 am1 = *reinterpret_cast<const uint4 *>(aim + (fr + 1) * 1024);
@@ -1161,7 +1041,7 @@ __global__ __launch_bounds__(512, 1) void k_sp50_dA(Sp50Params P) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) sv[j] = S[kk][8 * ks + j];
         uint4 sp[2];
-        spb_planes<2>(sv, sp);
+        spb_planes(sv, sp);
 #pragma unroll
         for (int wt = 0; wt < 2; ++wt) {
           dacc[kk][wt] = spb_mfma(sp[0], xv[wt], dacc[kk][wt]);
@@ -1216,45 +1096,43 @@ __global__ void k_pack_sp50_a(const float *A, __bf16 *img, int K) {
   }
 }
 
-// instantiated shapes: the NTU graph with spatial partitioning on the bf16 path
-// (BASELINE cfg3) and the Kinetics graph, uniform partition, on the fp32 split
-// path (cfg2)
-// The fp32 split variant is compiled but not selected: at K = 1 the H tensor is
-// only C_in channels and the unfused pair (fp32-MFMA H GEMM at 3.5 TB/s +
-// k_spatial_bwd5) is faster (cfg2 L1 281 vs 351 us, L8 421 vs 781 us; the
-// twelve split MFMAs per 16-channel chunk serialise behind each chunk's wait);
-// STGCN_SPB_X3 selects it (A/B only).
-bool sp_bwd_fused_supported(int C, int V, int K, int R, int T, bool x3) {
-  constexpr int D = SpBwdGeo<25, 3, false>::D, CMAX = SpBwdGeo<25, 3, false>::CMAX;
-  constexpr bool x3_on = STGCN_AB_SPB_X3 != 0;
+// instantiated shape: the NTU graph with spatial partitioning on the bf16 path
+// (BASELINE cfg3); V = 50 runs the k_sp50_dx / _dA pair.
+// The fp32 split path (cfg2, K = 1) stays unfused: there the H tensor is only
+// C_in channels and the unfused pair (fp32-MFMA H GEMM at 3.5 TB/s +
+// k_spatial_bwd5) measured faster than an exact-split form of this kernel (L1
+// 281 vs 351 us, L8 421 vs 781 us).
+bool sp_bwd_fused_supported(int C, int V, int K, int R, int T) {
+  constexpr int D = SpBwdGeo<25, 3>::D, CMAX = SpBwdGeo<25, 3>::CMAX;
   // V = 50: the k_sp50_dx / _dA pair re-reads dZ once per 32-channel block, so it
   // is selected up to C_in = 128 (cfg5 layer timings, kbench_spb.py: L1 1241 vs
   // 1516 us for the unfused H GEMM + k_spatial_bwd6, L4 1471 vs 1507, L5 1438 vs
   // 1596, but L8 (C_in = 256) 2156 vs 1819)
-  const bool shape = x3 ? (x3_on && V == 18 && K == 1)
-                        : (K == 3 && (V == 25 || (V == 50 && C <= 128)));
+  const bool shape = K == 3 && (V == 25 || (V == 50 && C <= 128));
   return shape && C > 0 && C % 32 == 0 && C <= CMAX && R % 16 == 0 && R / 16 >= D &&
          (int64_t)std::max(R, C) * T * V * 4 < ((int64_t)1 << 31);
 }
 
-// A-operand image bytes: V = 25 [k][ks][plane] (3 planes max), V = 50 [k][wt][vt][ks][plane]
+// A-operand image bytes: V = 25 [k][ks][plane] (room for 3 planes), V = 50 [k][wt][vt][ks][plane]
 static constexpr size_t kSpbAimgBytes = std::max<size_t>(3 * 2 * 3 * 1024, Sp50Geo<3>::AIMG);
 
+// (the W' term keeps the size of three bf16 planes although one is packed: the
+// workspace byte counts callers see are part of the ABI's observable behaviour)
 size_t sp_bwd_fused_wpk_bytes(int C, int R, int K, int V) {
   (void)V;
   return kSpbAimgBytes + (size_t)K * R * C * 2 * 3 + 256;
 }
 
-template <int V, int K, bool X3, bool DZB = false>
+template <int V, int K>
 static hipError_t launch_spb(const SpBwdParams &P0, hipStream_t s) {
-  using G = SpBwdGeo<V, K, X3, DZB>;
+  using G = SpBwdGeo<V, K>;
   SpBwdParams P = P0;
   P.nft = (P.T + G::FT - 1) / G::FT;
   const int64_t items = (int64_t)P.ncb * P.nft * P.nitems;  // (nitems: N on entry)
   if (items >= (int64_t)1 << 31) return hipErrorInvalidValue;
   P.nitems = (int)items;
   const int grid = (int)std::min<int64_t>(items, 256);
-  hipLaunchKernelGGL((k_sp_bwd_fused<V, K, X3, DZB>), dim3(grid), dim3(512), G::LDS, s, P);
+  hipLaunchKernelGGL((k_sp_bwd_fused<V, K>), dim3(grid), dim3(512), G::LDS, s, P);
   return hipGetLastError();
 }
 
@@ -1262,16 +1140,15 @@ hipError_t launch_sp_bwd_fused(const float *dZ, const float *x, const float *mea
                                const float *invstd, const float *g, const float *b,
                                const float *A, const float *W, void *wpk, float *dx, float *dA,
                                double *sd, double *sdn, int N, int C, int R, int T, int V, int K,
-                               int write_dx, int relu, bool x3, hipStream_t s,
-                               const PrevBn *prev, int dz_bf16, int only) {
-  if (!sp_bwd_fused_supported(C, V, K, R, T, x3)) return hipErrorInvalidValue;
-  const int npw = x3 ? 3 : 1, npa = x3 ? 3 : 2;
+                               int write_dx, int relu, hipStream_t s, const PrevBn *prev,
+                               int only) {
+  if (!sp_bwd_fused_supported(C, V, K, R, T)) return hipErrorInvalidValue;
   __bf16 *aimg = reinterpret_cast<__bf16 *>(wpk);
   __bf16 *wp = aimg + kSpbAimgBytes / 2;
-  hipLaunchKernelGGL(k_pack_spb_a, dim3(24), dim3(256), 0, s, A, aimg, K, V, npa);
-  const int64_t nw = (int64_t)K * R * C * npw;
+  hipLaunchKernelGGL(k_pack_spb_a, dim3(24), dim3(256), 0, s, A, aimg, K, V);
+  const int64_t nw = (int64_t)K * R * C;
   hipLaunchKernelGGL(k_pack_spb_w, dim3((unsigned)std::min<int64_t>((nw + 255) / 256, 1024)),
-                     dim3(256), 0, s, W, wp, K, R, C, npw);
+                     dim3(256), 0, s, W, wp, K, R, C);
   SpBwdParams P{};
   P.dZ = dZ;
   P.x = x;
@@ -1293,8 +1170,7 @@ hipError_t launch_sp_bwd_fused(const float *dZ, const float *x, const float *mea
   P.write_dx = write_dx;
   P.relu = relu;
   if (prev) P.prev = *prev;
-  if (V == 50) {  // the two-person graph: k_sp50_dx + k_sp50_dA (fp32 dZ only)
-    if (dz_bf16 || x3) return hipErrorInvalidValue;
+  if (V == 50) {  // the two-person graph: k_sp50_dx + k_sp50_dA
     using G = Sp50Geo<3>;
     hipLaunchKernelGGL(k_pack_sp50_a, dim3(48), dim3(256), 0, s, A, aimg, K);
     Sp50Params Q{};
@@ -1329,9 +1205,7 @@ hipError_t launch_sp_bwd_fused(const float *dZ, const float *x, const float *mea
     if (only != 1) hipLaunchKernelGGL((k_sp50_dA<3>), dim3(grid), dim3(512), G::LDS2, s, Q);
     return hipGetLastError();
   }
-  if (x3) return dz_bf16 ? hipErrorInvalidValue : launch_spb<18, 1, true>(P, s);
-  if (dz_bf16) return launch_spb<25, 3, false, true>(P, s);
-  return launch_spb<25, 3, false>(P, s);
+  return launch_spb<25, 3>(P, s);
 }
 
 }  // namespace stgcn

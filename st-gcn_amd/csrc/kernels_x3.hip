@@ -1145,8 +1145,8 @@ __global__ __launch_bounds__(NW * 64, (NPL == 1 || NW == 4) ? 2 : 1) void k_conv
       bna_contract<G::ROWS>(smem, arow);
       __syncthreads();
     }
-    // (one-plane bf16 path: the output may be stored in bf16, p.out_bf16 -- the
-    // data gradient dZ of capi.hip dz_bf16)
+    // (one-plane bf16 path: the epilogue can store the output in bf16, p.out_bf16;
+    // no caller sets it now that dZ stays in fp32)
     conv_tile_store_rows<V, G::NCOLS, G::NT, G::ROWS, NPL == 1, NPL != 1>(
         p, smem, smem + G::ROWS * kEpiPitch, n, r0, m0);
     return;
@@ -1332,11 +1332,10 @@ size_t conv_x3_wpk_bytes(const ConvGemmParams &p) {
 
 // 128-row tiles (two 32-row blocks per wave: half the weight and window
 // staging per MFMA, half the window re-reads over the row tiles) for the
-// 9-tap launches with a whole number of them and unit output stride
-// (STGCN_AB_X3_MR1 build: 64-row tiles everywhere, A/B measurement only)
+// 9-tap launches with a whole number of them and unit output stride (every
+// other launch: 64-row tiles)
 static bool x3_wide_rows(const ConvGemmParams &p) {
-  constexpr bool off = STGCN_AB_X3_MR1 != 0;
-  return !off && p.NQ == 9 && p.s_out == 1 && p.R % 128 == 0;
+  return p.NQ == 9 && p.s_out == 1 && p.R % 128 == 0;
 }
 // 4-wave 64-row tiles, two workgroups per CU (ConvX3Geo NW = 4): the fp16-split
 // stride-1 forward where the caller marked it (p.w4: capi.hip fwd_w4), up to 128
@@ -1344,8 +1343,7 @@ static bool x3_wide_rows(const ConvGemmParams &p) {
 // the overlap gains: L8 0.668 vs 0.654 ms, profiles/r6b_kbench_w4.txt). Decides
 // the packed weight layout (64-row tiles) and the kernel alike.
 static bool x3_w4(const ConvGemmParams &p, int npl) {
-  constexpr bool off = STGCN_AB_X3_NOW4 != 0;
-  return !off && p.w4 && npl == 2 && !p.spb && !p.bna && p.NQ == 9 && p.s_in == 1 &&
+  return p.w4 && npl == 2 && !p.spb && !p.bna && p.NQ == 9 && p.s_in == 1 &&
          p.s_out == 1 && (p.V == 18 || p.V == 25) && p.R <= 128;
 }
 template <int V>
@@ -1517,10 +1515,9 @@ hipError_t launch_conv_x3(const ConvGemmParams &p, hipStream_t s) {
 }
 
 // The bf16 temporal-conv GEMMs (9 taps; stride-2 data-gradient phases 5 / 4) on
-// the one-plane k_conv_x3 (STGCN_AB_OLD_BF16CONV build: k_conv_bf16, A/B only)
+// the one-plane k_conv_x3 (the one-tap GEMMs stay on k_conv_bf16, kernels_bf16.hip)
 bool conv_b1_supported(const ConvGemmParams &p) {
-  constexpr bool off = STGCN_AB_OLD_BF16CONV != 0;
-  if (off || p.C < 16) return false;
+  if (p.C < 16) return false;
   if (p.V != 18 && p.V != 25 && p.V != 50) return false;
   if (p.FT != kTileCols / p.V) return false;
   if (p.s_in == 2) return p.NQ == 9;
