@@ -30,7 +30,7 @@ import torch
 
 from conftest import rel_to_max
 from oracle import ref_cpu
-from test_gpu_block import DEV, _random_case
+from test_gpu_block import DEV, _random_case, _to_dev
 
 pytestmark = pytest.mark.gpu
 
@@ -39,12 +39,12 @@ TIE_BF16 = 2e-2
 FLOOR_FACTOR = 3.0
 
 
-def _run(pkg, arrays, x, g, bf16, need_dx=True):
+def _run(pkg, arrays, x, g, bf16, need_dx=True, to_dev=_to_dev):
     p, b = ref_cpu.block_params_from_arrays(arrays, dtype=torch.float32, requires_grad=False)
     stride, residual = int(arrays["meta"][2]), bool(arrays["meta"][7])
-    cu = {k: v.to(DEV).contiguous().requires_grad_(True) for k, v in p.items()}
-    bu = {k: v.to(DEV).clone() for k, v in b.items() if "num_batches" not in k}
-    xd = x.to(DEV).float().contiguous().requires_grad_(need_dx)
+    cu = {k: to_dev(v, k).contiguous().requires_grad_(True) for k, v in p.items()}
+    bu = {k: to_dev(v, k) for k, v in b.items() if "num_batches" not in k}  # (a copy: in/out)
+    xd = to_dev(x, "x").float().contiguous().requires_grad_(need_dx)
     common = (xd, cu["spatialConv.A"], cu["spatialConv.W.weight"], cu["spatialConv.W.bias"],
               cu["temporalConv.weight"], cu["temporalConv.bias"], cu["batch_n.weight"],
               cu["batch_n.bias"], cu["batch_n_2.weight"], cu["batch_n_2.bias"])
@@ -60,7 +60,7 @@ def _run(pkg, arrays, x, g, bf16, need_dx=True):
     # residual block: the inner ReLU's mask (Za = ReLU(BN2(Z)) > 0, saved by the
     # Function) so the oracle can take the same subgradient choices there too
     inner = (y.grad_fn.saved_tensors[2] > 0).cpu() if residual else None
-    y.backward(g.to(DEV).float())
+    y.backward(to_dev(g, "g").float())
     torch.cuda.synchronize()
     out = {"y": y.detach().cpu(), "inner_mask": inner}
     if need_dx:
@@ -99,6 +99,14 @@ def _check_bf16(pkg, case, residual=False, need_dx=True, seed=0):
     arrays, x, g = _random_case(pkg, C_in, C_out, stride, V, K, N, T, seed=seed,
                                 residual=residual)
     got = _run(pkg, arrays, x, g, bf16=True, need_dx=need_dx)
+    want, ref16 = _bf16_reference(arrays, got, need_dx)
+    f32 = _run(pkg, arrays, x, g, bf16=False, need_dx=need_dx)
+    return _gate_bf16(got, want, ref16, f32, residual)
+
+
+def _bf16_reference(arrays, got, need_dx=True):
+    """The ReLU tie checks of a bf16 run, then the fp64 oracle and the
+    reference with bf16 GEMM operands, both through the run's ReLU masks."""
     mask, inner = got["y"] > 0, got["inner_mask"]
     pre = ref_cpu.block_pre_relu(arrays)
     flips = mask != (pre > 0)
@@ -117,6 +125,13 @@ def _check_bf16(pkg, case, residual=False, need_dx=True, seed=0):
                                gemm_bf16=True, inner_mask=inner)
     if not need_dx:
         want.pop("grad.x")
+    return want, ref16
+
+
+def _gate_bf16(got, want, ref16, f32, residual):
+    """The bf16 gate: ``got`` against the fp64 oracle ``want`` with the
+    reference's own bf16-operand error ``ref16`` as floor, and against the
+    fp32 path's output ``f32`` of the same inputs."""
     errs = _errors(got, want, residual)
     floor = _errors(ref16, want, residual)
     bad = {k: (e, floor[k]) for k, e in errs.items() if not e < max(TOL_BF16, FLOOR_FACTOR * floor[k])}
@@ -124,7 +139,6 @@ def _check_bf16(pkg, case, residual=False, need_dx=True, seed=0):
     if not residual:
         assert got["grad.temporalConv.bias"].abs().max().item() < 1e-3
     # the bf16 kernels ran (results differ from the fp32 path) and sit in the bf16 band of it
-    f32 = _run(pkg, arrays, x, g, bf16=False, need_dx=need_dx)
     d = rel_to_max(got["y"].numpy(), f32["y"].numpy())
     assert 0 < d < TOL_BF16, f"bf16 vs fp32 path output difference {d}"
     return errs

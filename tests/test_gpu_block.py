@@ -28,7 +28,14 @@ TOL_RUNNING = 1e-5
 DEV = "cuda:0"
 
 
-def _fold_prep(pkg, cu, xshape, C_out, K, stride, gemm):
+def _to_dev(t, name):
+    """The default ``to_dev`` hook of the runners below: where a test input
+    (named as in the oracle's dicts: "x", "g", a parameter or running-statistic
+    key) lives on the GPU. test_gpu_poison.py places them in guarded memory."""
+    return t.to(DEV)
+
+
+def _fold_prep(pkg, cu, xshape, C_out, K, stride, gemm, empty=torch.empty):
     """ABI 7 stgcn_fold_prep of one folded block (as STGCNStack does per step)"""
     import ctypes
     hl = pkg.hip_lib
@@ -37,7 +44,7 @@ def _fold_prep(pkg, cu, xshape, C_out, K, stride, gemm):
                             **pkg.fused._gemm_flags(gemm))
     nbytes = lib.stgcn_fold_prep_bytes(ctypes.byref(d))
     assert nbytes > 0, "the block does not fold"
-    buf = torch.empty(nbytes, device=DEV, dtype=torch.uint8)
+    buf = empty(nbytes, device=DEV, dtype=torch.uint8)
     w = hl.FoldWeights(*[hl.ptr(cu[k]) for k in (
         "spatialConv.A", "spatialConv.W.weight", "spatialConv.W.bias", "temporalConv.weight",
         "temporalConv.bias")])
@@ -46,21 +53,24 @@ def _fold_prep(pkg, cu, xshape, C_out, K, stride, gemm):
     return buf
 
 
-def _run_hip(pkg, arrays, x, g, need_dx=True, gemm="fp32", prep=False):
+def _run_hip(pkg, arrays, x, g, need_dx=True, gemm="fp32", prep=False, to_dev=_to_dev):
     """Fused block fwd+bwd on the GPU; returns the oracle-style result dict.
     gemm: channel-GEMM arithmetic ("fp32", "f32x3", "bf16"; fused._gemm_flags).
-    prep: the folded block's weight operands from stgcn_fold_prep (ABI 7)."""
+    prep: the folded block's weight operands from stgcn_fold_prep (ABI 7).
+    to_dev: (tensor, name) -> GPU tensor, see ``_to_dev``; its optional
+    ``empty`` attribute allocates the fold-prep buffer."""
     p, b = ref_cpu.block_params_from_arrays(arrays, dtype=torch.float32, requires_grad=False)
     stride, residual = int(arrays["meta"][2]), bool(arrays["meta"][7])
-    cu = {k: v.to(DEV).contiguous().requires_grad_(True) for k, v in p.items()}
+    cu = {k: to_dev(v, k).contiguous().requires_grad_(True) for k, v in p.items()}
     cc = None
     if prep:
         with torch.no_grad():
             buf = _fold_prep(pkg, cu, x.shape, cu["temporalConv.weight"].shape[0],
-                             cu["spatialConv.A"].shape[0], stride, gemm)
+                             cu["spatialConv.A"].shape[0], stride, gemm,
+                             empty=getattr(to_dev, "empty", torch.empty))
         cc = pkg.fused.ChainCtx(prep=buf)
-    bu = {k: v.to(DEV).clone() for k, v in b.items() if "num_batches" not in k}
-    xd = x.to(DEV).float().contiguous().requires_grad_(need_dx)
+    bu = {k: to_dev(v, k) for k, v in b.items() if "num_batches" not in k}  # (a copy: in/out)
+    xd = to_dev(x, "x").float().contiguous().requires_grad_(need_dx)
     common = (xd, cu["spatialConv.A"], cu["spatialConv.W.weight"], cu["spatialConv.W.bias"],
               cu["temporalConv.weight"], cu["temporalConv.bias"], cu["batch_n.weight"],
               cu["batch_n.bias"], cu["batch_n_2.weight"], cu["batch_n_2.bias"])
@@ -73,7 +83,7 @@ def _run_hip(pkg, arrays, x, g, need_dx=True, gemm="fp32", prep=False):
     else:
         y = pkg.fused.StgcnBlockFn.apply(*common, *running, stride, 4, 1e-5, 0.1, True,
                                          cc, 0.0, gemm)
-    y.backward(g.to(DEV).float())
+    y.backward(to_dev(g, "g").float())
     torch.cuda.synchronize()
     out = {"y": y.detach().cpu()}
     if need_dx:
@@ -354,15 +364,15 @@ def _keep_mask(seed, shape, p):
     return torch.from_numpy(((z >> np.uint64(32)) >= np.uint64(thresh)).reshape(shape))
 
 
-def _run_hip_dropout(pkg, arrays, x, g, drop):
+def _run_hip_dropout(pkg, arrays, x, g, drop, to_dev=_to_dev):
     torch.manual_seed(1234)
     seed = int(torch.randint(0, 2 ** 62, (1,)).item())   # fused._dropout_seed's draw
     torch.manual_seed(1234)
     p, b = ref_cpu.block_params_from_arrays(arrays, dtype=torch.float32, requires_grad=False)
     stride, residual = int(arrays["meta"][2]), bool(arrays["meta"][7])
-    cu = {k: v.to(DEV).contiguous().requires_grad_(True) for k, v in p.items()}
-    bu = {k: v.to(DEV).clone() for k, v in b.items() if "num_batches" not in k}
-    xd = x.to(DEV).float().contiguous().requires_grad_(True)
+    cu = {k: to_dev(v, k).contiguous().requires_grad_(True) for k, v in p.items()}
+    bu = {k: to_dev(v, k) for k, v in b.items() if "num_batches" not in k}  # (a copy: in/out)
+    xd = to_dev(x, "x").float().contiguous().requires_grad_(True)
     common = (xd, cu["spatialConv.A"], cu["spatialConv.W.weight"], cu["spatialConv.W.bias"],
               cu["temporalConv.weight"], cu["temporalConv.bias"], cu["batch_n.weight"],
               cu["batch_n.bias"], cu["batch_n_2.weight"], cu["batch_n_2.bias"])
@@ -375,7 +385,7 @@ def _run_hip_dropout(pkg, arrays, x, g, drop):
     else:
         y = pkg.fused.StgcnBlockFn.apply(*common, *running, stride, 4, 1e-5, 0.1, True,
                                          None, drop)
-    y.backward(g.to(DEV).float())
+    y.backward(to_dev(g, "g").float())
     torch.cuda.synchronize()
     out = {"y": y.detach().cpu(), "grad.x": xd.grad.cpu()}
     for k, t in cu.items():
@@ -400,6 +410,10 @@ def test_block_dropout_matches_oracle(pkg, case):
     arrays, x, g = _random_case(pkg, C_in, C_out, stride, V, K, N, T, seed=5,
                                 residual=residual)
     got, seed = _run_hip_dropout(pkg, arrays, x, g, drop)
+    _gate_dropout(arrays, got, seed, drop, residual)
+
+
+def _gate_dropout(arrays, got, seed, drop, residual):
     keep = _keep_mask(seed, tuple(got["y"].shape), drop)
     # mask statistics: the fraction kept is 1-p (binomial, 6 sigma)
     n = keep.numel()

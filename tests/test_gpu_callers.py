@@ -26,7 +26,7 @@ import torch
 
 from conftest import GOLDEN, load_npz, rel_to_max
 from oracle import ref_cpu
-from test_gpu_block import DEV, TOL, _random_case
+from test_gpu_block import DEV, TOL, _random_case, _to_dev
 from test_gpu_stack import capture_relu_masks, check_relu_ties, gate_stack_grads, \
     oracle_through_masks
 from test_oracle_extra import legacy_running_stats
@@ -38,7 +38,7 @@ def _spatial_fixtures():
     return sorted(os.path.basename(p) for p in glob.glob(os.path.join(GOLDEN, "spatialconv_*.npz")))
 
 
-def _spatial_run(pkg, arrays, bf16=False):
+def _spatial_run(pkg, arrays, bf16=False, to_dev=_to_dev, x_grad=True):
     C_in, C_out = int(arrays["meta"][0]), int(arrays["meta"][1])
     A = torch.from_numpy(arrays["param.A"])
     torch.manual_seed(0)
@@ -46,11 +46,16 @@ def _spatial_run(pkg, arrays, bf16=False):
     sc.load_state_dict({k[len("param."):]: torch.from_numpy(v) for k, v in arrays.items()
                         if k.startswith("param.")})
     sc = sc.to(DEV)
-    x = torch.from_numpy(arrays["x"]).to(DEV).requires_grad_(True)
+    if to_dev is not _to_dev:
+        for k, v in sc.named_parameters():
+            v.data = to_dev(v.data.cpu(), k)
+    x = to_dev(torch.from_numpy(arrays["x"]), "x").requires_grad_(x_grad)
     y = sc(x)
-    y.backward(torch.from_numpy(arrays["g"]).to(DEV))
+    y.backward(to_dev(torch.from_numpy(arrays["g"]), "g"))
     torch.cuda.synchronize()
-    out = {"y": y.detach().cpu(), "grad.x": x.grad.cpu()}
+    out = {"y": y.detach().cpu()}
+    if x_grad:
+        out["grad.x"] = x.grad.cpu()
     for k, p in sc.named_parameters():
         out["grad." + k] = p.grad.cpu()
     return out
@@ -150,6 +155,12 @@ def _eval_case(pkg, case, residual, seed=0):
 def test_block_eval_mode_backward(pkg, case, residual, gemm):
     """Eval mode with gradients (frozen BatchNorm statistics): the backward
     treats the running statistics as constants, like nn.BatchNorm2d.eval()."""
+    _check_eval_backward(pkg, case, residual, gemm)
+
+
+def _check_eval_backward(pkg, case, residual, gemm, to_dev=_to_dev):
+    """to_dev: (tensor, name) -> GPU tensor (test_gpu_block._to_dev); another hook
+    also re-places the module's parameters and buffers."""
     arrays, x, g = _eval_case(pkg, case, residual)
     p, b = ref_cpu.block_params_from_arrays(arrays, dtype=torch.float32, requires_grad=False)
     stride = case[2]
@@ -165,9 +176,12 @@ def test_block_eval_mode_backward(pkg, case, residual, gemm):
     sd.update({k: v for k, v in b.items()})
     blk.load_state_dict(sd)
     blk = blk.to(DEV).eval()
-    xd = x.to(DEV).requires_grad_(True)
+    if to_dev is not _to_dev:
+        for k, v in list(blk.named_parameters()) + list(blk.named_buffers()):
+            v.data = to_dev(v.data.cpu(), k)
+    xd = to_dev(x, "x").requires_grad_(True)
     y = blk(xd)
-    y.backward(g.to(DEV))
+    y.backward(to_dev(g, "g"))
     torch.cuda.synchronize()
 
     def oracle(dtype, gemm_bf16=False):
@@ -191,7 +205,7 @@ def test_block_eval_mode_backward(pkg, case, residual, gemm):
                 for k, w in want.items()}
         blk.gemm_dtype = torch.float32
         with torch.no_grad():
-            y32 = blk(x.to(DEV))
+            y32 = blk(to_dev(x, "x"))
         assert not torch.equal(y32.cpu(), got["y"]), "bf16 kernels did not run"
     else:
         gate = {k: (TOL if k in ("y", "grad.x") else 2 * TOL) for k in want}

@@ -566,10 +566,9 @@ def test_stack_chain_matches_unchained_bf16x3(pkg, residual, f32_gemm):
     assert not bad, "; ".join(bad)
 
 
-def _bf16_stack_errors(pkg, V, seed, N, T, classes=60):
-    """One bf16 stack training step (K = 3 spatial partitioning) vs the fp64
-    oracle, and the reference's own bf16-operand error (ref_cpu gemm_bf16) on
-    the same inputs: ({tensor: err}, {tensor: floor})."""
+def _bf16_stack_setup(pkg, V, seed, N, T, classes=60):
+    """The bf16 stack (K = 3 spatial partitioning, on the CPU still) and inputs of
+    ``_bf16_stack_errors``: (A, model, x NTVC, labels, initial parameters)."""
     gr = pkg.graph
     A = gr.get_normalized_adjacency_matrices(2, 1, distances=gr.synthetic_distances(V),
                                              graph=gr.graph_for(V))
@@ -579,11 +578,12 @@ def _bf16_stack_errors(pkg, V, seed, N, T, classes=60):
     x = torch.randn(N, T, V, 3, generator=torch.Generator().manual_seed(seed + 1))
     lab = torch.randint(0, classes, (N,), generator=torch.Generator().manual_seed(seed + 2))
     params0 = {k: v.detach().clone() for k, v in model.named_parameters()}
-    model = model.cuda().train()
-    loss, logits = model.forward_loss(x.cuda().permute(0, 3, 1, 2).contiguous(), lab.cuda())
-    loss.backward()
-    torch.cuda.synchronize()
+    return A, model, x, lab, params0
 
+
+def _bf16_stack_oracle(A, params0, x, lab, seed, classes=60):
+    """(logits, loss, grads) of the fp64 oracle and of the reference with bf16
+    GEMM operands for one training step from ``params0``."""
     def oracle(dtype, bf16):
         p = {k: v.clone().to(dtype).requires_grad_(True) for k, v in params0.items()}
         _, b = ref_cpu.init_stack_params(3, classes, A, seed=seed)
@@ -594,8 +594,13 @@ def _bf16_stack_errors(pkg, V, seed, N, T, classes=60):
         ls.backward()
         return lg.detach(), ls.detach(), {k: v.grad for k, v in p.items()}
 
-    l64, loss64, g64 = oracle(torch.float64, False)
-    l16, loss16, g16 = oracle(torch.float32, True)
+    return oracle(torch.float64, False), oracle(torch.float32, True)
+
+
+def _bf16_stack_vs_oracle(model, loss, logits, oracles):
+    """({tensor: err}, {tensor: floor}) of a stack's step (loss, logits and the
+    gradients on ``model``) against ``_bf16_stack_oracle``'s pair."""
+    (l64, loss64, g64), (l16, loss16, g16) = oracles
     errs = {"logits": rel_to_max(logits.detach().cpu().numpy(), l64.numpy()),
             "loss": abs(loss.item() - loss64.item())}
     floor = {"logits": rel_to_max(l16.numpy(), l64.numpy()),
@@ -608,6 +613,19 @@ def _bf16_stack_errors(pkg, V, seed, N, T, classes=60):
         errs[k] = rel_to_max(v.grad.detach().cpu().double().numpy(), want)
         floor[k] = rel_to_max(g16[k].detach().double().numpy(), want)
     return errs, floor
+
+
+def _bf16_stack_errors(pkg, V, seed, N, T, classes=60):
+    """One bf16 stack training step (K = 3 spatial partitioning) vs the fp64
+    oracle, and the reference's own bf16-operand error (ref_cpu gemm_bf16) on
+    the same inputs: ({tensor: err}, {tensor: floor})."""
+    A, model, x, lab, params0 = _bf16_stack_setup(pkg, V, seed, N, T, classes)
+    model = model.cuda().train()
+    loss, logits = model.forward_loss(x.cuda().permute(0, 3, 1, 2).contiguous(), lab.cuda())
+    loss.backward()
+    torch.cuda.synchronize()
+    return _bf16_stack_vs_oracle(model, loss, logits,
+                                 _bf16_stack_oracle(A, params0, x, lab, seed, classes))
 
 
 @pytest.mark.parametrize("V", [25, 50])
