@@ -3575,8 +3575,7 @@ static bool launch_bwd56(const float *H, const float *x, const float *mean, cons
     else if (V == 25)
       done = STGCN_BWD5(25, 128, 1) || STGCN_BWD5(25, 64, 1) || STGCN_BWD5(25, 128, 2) ||
              STGCN_BWD5(25, 64, 2) || STGCN_BWD5(25, 128, 3) || STGCN_BWD5(25, 64, 3);
-    else if (V == 50)
-      done = STGCN_BWD5(50, 64, 1) || STGCN_BWD5(50, 64, 2) || STGCN_BWD5(50, 64, 3);
+    // (V = 50: K * 25 * 2 > 48 for every K, so the guard above sends it to bwd6)
 #undef STGCN_BWD5
     if (done) return true;
   }

@@ -30,6 +30,9 @@ Outputs (small .npz files next to this script):
   --only data     regenerate data_pipeline.npz only.
   --only extra    regenerate the round-2 fixtures only (spatialconv_*,
                   stack_cfg1_edge, legacy_stgcn).
+  --only k2       generate the K = 2 fixtures only (distance partitioning,
+                  d = 1: the block_* / spatialconv_* cases named *k2), with A
+                  from the committed adjacency.npz; every other file untouched.
 """
 import argparse
 import os
@@ -139,6 +142,12 @@ BLOCK_CASES = [
     ("b3x64_v50k3", 3, 64, 1, 50, 2, 2, 12, False),
     ("res64x64_v18", 64, 64, 1, 18, 0, 2, 20, True),
     ("res64x128s2_v18", 64, 128, 2, 18, 0, 2, 20, True),
+    # distance partitioning (strategy 1, d = 1): K = 2
+    ("b64x64_v25k2", 64, 64, 1, 25, 1, 2, 12, False),
+    # (stride 2, odd T; 64 output channels keep the file small: at 128 the two
+    # 128 x 128 x 9 temporal weight tensors alone are 1.2 MB, and the partitioned
+    # SpatialConv half, C_in * T = 832 rows of V = 18, is the same)
+    ("b64x64s2_v18k2", 64, 64, 2, 18, 1, 2, 13, False),
 ]
 
 
@@ -212,6 +221,7 @@ SPATIAL_CASES = [
     ("s3x64_v18", 3, 64, 18, 0, 2, 20),
     ("s64x64_v25k3", 64, 64, 25, 2, 2, 16),
     ("s64x128_v50k3", 64, 128, 50, 2, 2, 9),
+    ("s64x64_v18k2", 64, 64, 18, 1, 2, 12),     # distance partitioning: K = 2
 ]
 
 
@@ -345,7 +355,7 @@ def make_data_pipeline(util, augmentation, calc):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("reference", nargs="?", default="/root/reference")
-    ap.add_argument("--only", choices=["data", "extra"], default=None)
+    ap.add_argument("--only", choices=["data", "extra", "k2"], default=None)
     args = ap.parse_args()
     _install_stubs()
     sys.path.insert(0, os.path.join(args.reference, "src"))
@@ -364,12 +374,22 @@ def main():
         import lightning_model  # noqa: E402
         from network import stgcn  # noqa: E402
     torch.set_num_threads(8)
-    if args.only == "extra":  # round-2 fixtures (round-1 files untouched)
+    if args.only in ("extra", "k2"):  # (the other fixtures stay untouched)
         with np.load(os.path.join(HERE, "adjacency.npz")) as f:
             mats = {k: f[k] for k in f.files}
     else:
         with tempfile.TemporaryDirectory() as tmp:
             mats = make_adjacency(adjacency, tmp)
+    if args.only == "k2":
+        with contextlib.redirect_stdout(io.StringIO()):
+            for case in BLOCK_CASES:
+                if case[0].endswith("k2"):
+                    make_block(st_graphconv, mats, *case)
+            for case in SPATIAL_CASES:
+                if case[0].endswith("k2"):
+                    make_spatialconv(st_graphconv, mats, *case)
+        print("wrote the K = 2 fixtures to", HERE)
+        return
     with contextlib.redirect_stdout(io.StringIO()):
         if args.only != "extra":
             for case in BLOCK_CASES:

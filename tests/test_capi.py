@@ -67,6 +67,28 @@ def test_check_desc_rejects(pkg, lib, kw, code):
     assert lib.stgcn_fwd_workspace_bytes(ctypes.byref(d)) == 0
 
 
+@pytest.mark.parametrize("flags", [0, 2, 4, 12])
+def test_check_desc_partition_counts(pkg, lib, flags):
+    """K = 1..4 at V = 18 / 25 / 50 (the descriptors of test_gpu_partitions.py's
+    matrix, every GEMM mode): accepted, with workspaces and a plan; V = 50 with
+    K = 4 has K * V * V = 10000 > 8192 and is refused as unsupported."""
+    from partition_cases import CASES, MATRIX
+    for cid in MATRIX:
+        C_in, C_out, stride, V, _, K, N, T = CASES[cid]
+        d = _desc(pkg, N=N, C_in=C_in, C_out=C_out, T=T, T_out=(T - 1) // stride + 1, V=V, K=K,
+                  stride=stride, flags=flags)
+        assert lib.stgcn_check_desc(ctypes.byref(d)) == 0, (cid, lib.stgcn_last_error())
+        assert lib.stgcn_fwd_workspace_bytes(ctypes.byref(d)) > 0, cid
+        assert lib.stgcn_bwd_workspace_bytes(ctypes.byref(d)) > 0, cid
+        pkg.hip_lib.block_plan(d)
+    d = _desc(pkg, N=2, T=8, T_out=8, V=50, K=4, flags=flags)
+    assert lib.stgcn_check_desc(ctypes.byref(d)) == -2
+    assert b"K*V*V" in lib.stgcn_last_error()
+    assert lib.stgcn_fwd_workspace_bytes(ctypes.byref(d)) == 0
+    with pytest.raises(RuntimeError, match=r"failed \(-2\)"):
+        pkg.hip_lib.block_plan(d)
+
+
 def test_null_arguments_fail_without_touching_gpu(pkg, lib):
     d = _desc(pkg)
     args = pkg.hip_lib.FwdArgs()

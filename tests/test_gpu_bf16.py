@@ -94,12 +94,16 @@ def _pre_inner(arrays):
         return ref_cpu._bn(f, p, b, "batch_n_2", True, 0.1, 1e-5)
 
 
-def _check_bf16(pkg, case, residual=False, need_dx=True, seed=0):
+def _check_bf16(pkg, case, residual=False, need_dx=True, seed=0, A=None, floor_out=None):
+    """A: the block's adjacency (default: _random_case's). floor_out: a dict that
+    receives the bf16-operand oracle's own errors (the gate's floors)."""
     C_in, C_out, stride, V, K, N, T = case
     arrays, x, g = _random_case(pkg, C_in, C_out, stride, V, K, N, T, seed=seed,
-                                residual=residual)
+                                residual=residual, A=A)
     got = _run(pkg, arrays, x, g, bf16=True, need_dx=need_dx)
     want, ref16 = _bf16_reference(arrays, got, need_dx)
+    if floor_out is not None:
+        floor_out.update(_errors(ref16, want, residual))
     f32 = _run(pkg, arrays, x, g, bf16=False, need_dx=need_dx)
     return _gate_bf16(got, want, ref16, f32, residual)
 

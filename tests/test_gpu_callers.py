@@ -90,7 +90,10 @@ def test_spatialconv_standalone_matches_reference(pkg, fixture):
 def test_spatialconv_standalone_bf16(pkg):
     """bf16 channel GEMMs (SURVEY §8c gate 2e-2, or 3x the reference run with
     bf16 conv operands where that is further from exact)."""
-    ref = load_npz("spatialconv_s64x64_v25k3.npz")
+    _check_spatial_bf16(pkg, load_npz("spatialconv_s64x64_v25k3.npz"))
+
+
+def _check_spatial_bf16(pkg, ref):
     got = _spatial_run(pkg, ref, bf16=True)
     want = _spatial_oracle(ref, torch.float64)
     ref16 = _spatial_oracle(ref, torch.float32, gemm_bf16=True)
@@ -100,6 +103,46 @@ def test_spatialconv_standalone_bf16(pkg):
         floor = rel_to_max(ref16[k].double().numpy(), w.double().numpy())
         assert err < max(2e-2, 3 * floor), (k, err, floor)
     assert not torch.equal(got["y"], f32["y"]), "bf16 kernels did not run"
+
+
+def test_spatialconv_standalone_bf16_k2(pkg):
+    """The reference's K = 2 fixture (distance partitioning at V = 18) with bf16
+    channel GEMMs, gated as test_spatialconv_standalone_bf16."""
+    _check_spatial_bf16(pkg, load_npz("spatialconv_s64x64_v18k2.npz"))
+
+
+def _spatial_case_k4(pkg):
+    """SpatialConv 64 -> 64 at V = 25 with the K = 4 adjacency (distance
+    partitioning, depth 3), N = 2, T = 12, random parameters: a fixture-style
+    dict for ``_spatial_run`` / ``_spatial_oracle``."""
+    gr = pkg.graph
+    A = gr.get_normalized_adjacency_matrices(1, 3, graph=gr.graph_for(25))
+    assert tuple(A.shape) == (4, 25, 25)
+    torch.manual_seed(0)
+    sc = pkg.SpatialConv(64, 64, A)
+    arrays = {"param." + k: v.detach().numpy() for k, v in sc.state_dict().items()}
+    arrays["meta"] = np.array([64, 64, 25, 1, 2, 12])
+    arrays["x"] = torch.randn(2, 64, 12, 25, generator=torch.Generator().manual_seed(1)).numpy()
+    arrays["g"] = torch.randn(2, 64, 12, 25, generator=torch.Generator().manual_seed(2)).numpy()
+    return arrays
+
+
+def test_spatialconv_standalone_k4(pkg):
+    """stgcn_spatial_fwd / _bwd with more than three partitions (the generic
+    k_spatial_dx; no reference fixture: the fp64 oracle at the fp32 gate)."""
+    ref = _spatial_case_k4(pkg)
+    got = _spatial_run(pkg, ref)
+    want = _spatial_oracle(ref, torch.float64)
+    ref32 = _spatial_oracle(ref, torch.float32)
+    for k, w in want.items():
+        err = rel_to_max(got[k].double().numpy(), w.double().numpy())
+        floor = rel_to_max(ref32[k].double().numpy(), w.double().numpy())
+        assert floor <= TOL, (k, floor)   # (the gate stays at 2e-5 at most)
+        assert err < max(TOL, 2 * floor), (k, err, floor)
+
+
+def test_spatialconv_standalone_k4_bf16(pkg):
+    _check_spatial_bf16(pkg, _spatial_case_k4(pkg))
 
 
 def test_spatialconv_input_without_grad(pkg):

@@ -289,27 +289,45 @@ def test_stack_chain_matches_unchained(pkg, residual, drop):
             assert rel_to_max(a.cpu().numpy(), b.cpu().numpy()) < 1e-5, k
 
 
-@pytest.mark.parametrize("V,K,gemm,T", [(18, 1, "fp32", 40), (18, 1, "x3", 300),
-                                         (18, 1, "f16", 300),
-                                         # the reference's default graph: V = 25,
-                                         # unilabeling (K = 1), folded, unfused
-                                         # SpatialConv backward
-                                         (25, 1, "f16", 60), (25, 1, "x3", 40),
-                                         (25, 3, "bf16", 40), (50, 3, "bf16", 24),
-                                         (25, 3, "fp32", 40)])
-def test_stack_deferred_dx_matches_unchained(pkg, monkeypatch, V, K, gemm, T):
+UNI, DISTANCE, SPATIAL = 0, 1, 2   # graph.Strategy: K = 1, d + 1, 3 partitions
+
+
+def stack_adjacency(pkg, V, strat, d=1):
+    """The package's normalised (K, V, V) adjacency by (V, strategy, depth)."""
+    gr = pkg.graph
+    return gr.get_normalized_adjacency_matrices(strat, d, distances=gr.synthetic_distances(V),
+                                                graph=gr.graph_for(V))
+
+
+def _dx_row(V, strat, d, gemm, T):
+    K = {UNI: 1, DISTANCE: d + 1, SPATIAL: 3}[strat]
+    return pytest.param(V, strat, d, gemm, T, id=f"{V}-{K}-{gemm}-{T}")
+
+
+@pytest.mark.parametrize("V,strat,d,gemm,T", [
+    _dx_row(18, UNI, 1, "fp32", 40), _dx_row(18, UNI, 1, "x3", 300),
+    _dx_row(18, UNI, 1, "f16", 300),
+    # the reference's default graph: V = 25, unilabeling (K = 1), folded, unfused
+    # SpatialConv backward
+    _dx_row(25, UNI, 1, "f16", 60), _dx_row(25, UNI, 1, "x3", 40),
+    _dx_row(25, SPATIAL, 1, "bf16", 40), _dx_row(50, SPATIAL, 1, "bf16", 24),
+    _dx_row(25, SPATIAL, 1, "fp32", 40),
+    # K = 2 (distance partitioning) and V = 18 at K = 3: the fused bf16 forward
+    # with the H GEMM + k_spatial_bwd5 in prev mode (V = 25), the unfused bf16
+    # forward with k_spatial_bwd6<50, 2, true> (V = 50), k_spatial_bwd5<18, *, 3|2>
+    # on the fp32 and split paths. Every link defers: C * T is a multiple of 64
+    # at every block, the element counts are multiples of 4 and K <= 3
+    # (kernels.hip spatial_dx_prev_supported)
+    _dx_row(25, DISTANCE, 1, "bf16", 40), _dx_row(18, SPATIAL, 1, "fp32", 40),
+    _dx_row(18, DISTANCE, 1, "x3", 40), _dx_row(50, DISTANCE, 1, "bf16", 24)])
+def test_stack_deferred_dx_matches_unchained(pkg, monkeypatch, V, strat, d, gemm, T):
     """ABI 5 deferred dx: inside the chained stack every block's BN1 backward
     apply is folded into the previous block's ReLU+BN2 backward pass (dx keeps
     dxhat; the spatial backward reads the previous block's U: k_spatial_bwd5 at
     V = 18 / 25 fp32, k_sp_bwd_fused at V = 25 bf16, k_spatial_bwd6 at V = 50).
     The chained stack must equal the blocks run one by one, and the deferral
     must have run on every link."""
-    gr = pkg.graph
-    if K == 1:
-        A = gr.get_normalized_adjacency_matrices(0, 1, graph=gr.graph_for(V))
-    else:
-        A = gr.get_normalized_adjacency_matrices(2, 1, distances=gr.synthetic_distances(V),
-                                                 graph=gr.graph_for(V))
+    A = stack_adjacency(pkg, V, strat, d)
     kw = dict(gemm_dtype=torch.bfloat16 if gemm == "bf16" else torch.float32,
               f32_gemm={"x3": "bf16x3", "f16": "f16x2"}.get(gemm, "mfma"))
     deferred = []
@@ -804,8 +822,12 @@ def test_stack_frozen_first_blocks(pkg):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("V", [25, 50])
-def test_stack_lazy_links_bf16(pkg, V):
+@pytest.mark.parametrize("V,strat", [
+    pytest.param(25, SPATIAL, id="25"), pytest.param(50, SPATIAL, id="50"),
+    # K = 2: x_from_u rests on spatial_dx_prev_supported (the H GEMM + k_spatial_bwd5
+    # in prev mode), not on the fused spatial backward
+    pytest.param(25, DISTANCE, id="25-k2")])
+def test_stack_lazy_links_bf16(pkg, V, strat):
     """ABI 8 on the bf16 blocks (cfg3 / cfg5, verdict r5 item 4): every block
     output that only the next block reads stays unwritten -- the next block's
     fused spatial forward (k_sp_fwd_bf16 / k_sp_fwd_wide) forms
@@ -813,9 +835,7 @@ def test_stack_lazy_links_bf16(pkg, V):
     prev mode -- and the last output is pooled from U by the fused head. Loss,
     logits and running stats are bit-identical to the stack that writes every
     output; gradients agree to the order of the atomic adds."""
-    gr = pkg.graph
-    A = gr.get_normalized_adjacency_matrices(2, 1, distances=gr.synthetic_distances(V),
-                                             graph=gr.graph_for(V))
+    A = stack_adjacency(pkg, V, strat)
     torch.manual_seed(11)
     with contextlib.redirect_stdout(io.StringIO()):
         m1 = pkg.STGCNStack(3, 60, A, gemm_dtype=torch.bfloat16).cuda().train()
@@ -824,6 +844,11 @@ def test_stack_lazy_links_bf16(pkg, V):
     m2.lazy_links = False
     x = torch.randn(4, 3, 40, V, generator=torch.Generator().manual_seed(12)).cuda()
     lab = torch.randint(0, 60, (4,), generator=torch.Generator().manual_seed(13)).cuda()
+    hl = pkg.hip_lib
+    plans = [hl.block_plan(d) for d in pkg.fused.stack_descs(list(m1.conv), tuple(x.shape))]
+    assert all(p & hl.PLAN_X_FROM_U for p in plans[1:]), plans   # (block 0: C_in = 3)
+    if strat != SPATIAL:  # ... without the fused spatial backward
+        assert not any(p & hl.PLAN_SP_BWD_FUSED for p in plans), plans
     flags = pkg.fused.lazy_links(list(m1.conv), tuple(x.shape))
     assert flags == [True] * 9 + [False], flags
     for step in range(2):
