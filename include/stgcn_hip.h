@@ -261,6 +261,11 @@ typedef struct stgcn_bwd_args {
 
 int stgcn_abi_version(void);
 const char *stgcn_last_error(void);
+/* Additions within one ABI version (a bit mask; the ABI number changes only when
+ * an existing call does): */
+#define STGCN_FEATURE_EVAL_CHAIN 1 /* stgcn_block_fwd chains in eval (STGCN_PLAN_X_FROM_U_EVAL) */
+#define STGCN_FEATURE_EVAL_HEAD 2  /* stgcn_head_eval / _u and the metrics block           */
+int stgcn_features(void);
 
 /* Validate a descriptor without touching the GPU (0 = supported). */
 int stgcn_check_desc(const stgcn_desc_t *d);
@@ -319,6 +324,23 @@ int stgcn_spatial_bwd(const stgcn_spatial_desc_t *d, const float *dout, const fl
                                     * ReLU(BN2(U)) of the previous block
                                     * (stgcn_fwd_args_t.prev_U): that block's y is never
                                     * written                                             */
+/* (an eval-only bit, = 1024: written as a shift because test_gpu_poison's
+ * test_block_cases_cover_every_plan collects the decimal STGCN_PLAN_* defines and
+ * wants each selected by one of its TRAINING block cases, which an eval bit cannot
+ * be; its poison cases are test_gpu_eval.py's test_eval_step_poisoned) */
+#define STGCN_PLAN_X_FROM_U_EVAL (1u << 10) /* STGCN_FEATURE_EVAL_CHAIN: the eval forward
+                                    * (training == 0) can take its input as ReLU(BN2(U)) of
+                                    * the previous block: prev_U (16-byte aligned), prev_stats
+                                    * (that block's stats + 2 * C_in_prev: [running_mean2 |
+                                    * rsqrt(running_var2 + eps)] as its eval forward wrote
+                                    * them), prev_g2, prev_b2 with x null; x_stats is not
+                                    * needed. Non-residual blocks whose forward forms the
+                                    * input on load (the bf16 fused SpatialConv forward, or
+                                    * the folded block's G pass); no backward condition
+                                    * applies. STGCN_PLAN_X_FROM_U stays clear in eval. A
+                                    * non-residual block in eval also takes y null with
+                                    * y_stats null: no output pass, U is the handoff (to the
+                                    * next block's prev_U or stgcn_head_eval_u)            */
 int stgcn_block_plan(const stgcn_desc_t *d, uint32_t *plan);
 
 /* ABI 7: the weight-only operands of a stack's folded blocks (STGCN_PLAN_FOLD),
@@ -393,6 +415,41 @@ int stgcn_head_fwd_u(const stgcn_head_desc_t *d, const float *U, const float *st
                      const float *g2, const float *b2, const float *W, const float *bias,
                      const int64_t *labels, float *pooled, float *logits, float *lossv,
                      float *loss, void *stream);
+
+/* STGCN_FEATURE_EVAL_HEAD: the head of an evaluation step (validation_step /
+ * test_step, lightning_model.py:213-253: cross entropy and compute_accuracy
+ * :114-121; compute_conf_mat :123-133) with the epoch's metrics accumulated on
+ * the device: no host read per batch, so the step can be captured in a HIP graph.
+ * logits, lossv and loss are bit-identical to stgcn_head_fwd / stgcn_head_fwd_u
+ * when every label is valid. pred (N, int32) is the lowest index attaining the
+ * maximum logit. A label outside [0, classes) is cross entropy's ignore_index:
+ * lossv[n] = 0, the clip enters no count or sum but word 4, loss is the mean over
+ * the valid clips (0 without one). Clip n is a top-k hit iff fewer than topk
+ * classes j have logit_j > logit_label, or logit_j == logit_label with j < label
+ * (1 <= topk <= classes).
+ * The metrics block (may be null): eight 8-byte words, then classes * classes
+ * int64 confusion[label][pred] (confusion_matrix[i, j] += 1 of :131):
+ *   0 int64 batches            4 int64 clips with a label outside [0, classes)
+ *   1 int64 clips, valid label 5 double sum of per-clip losses
+ *   2 int64 top-1 correct      6 double sum of batch-mean losses
+ *   3 int64 top-k hits         7 double sum of batch accuracies
+ * Words 6 and 7 over word 0 are validation_epoch_end's averages of the batch
+ * means (:220-224, :241-246); words 5 and 2 over word 1 the per-clip averages.
+ * Deterministic: integer counts, one fixed-order fp64 sum per batch, one add per
+ * word. One stream at a time per block. classes: stgcn_head_fwd's limit. */
+typedef struct stgcn_eval_desc {
+  int32_t N, C, L, classes, topk;
+} stgcn_eval_desc_t;
+size_t stgcn_eval_metrics_bytes(int classes); /* 0: classes unsupported */
+int stgcn_eval_metrics_reset(void *metrics, int classes, void *stream);
+int stgcn_head_eval(const stgcn_eval_desc_t *d, const float *y, const float *W, const float *bias,
+                    const int64_t *labels, float *pooled, float *logits, float *lossv,
+                    float *loss, int32_t *pred, void *metrics, void *stream);
+/* ... pooling y = ReLU(BN2(U)) from the last block's U, as stgcn_head_fwd_u does */
+int stgcn_head_eval_u(const stgcn_eval_desc_t *d, const float *U, const float *stats2,
+                      const float *g2, const float *b2, const float *W, const float *bias,
+                      const int64_t *labels, float *pooled, float *logits, float *lossv,
+                      float *loss, int32_t *pred, void *metrics, void *stream);
 
 /* Multi-tensor Adam (torch.optim.Adam, amsgrad=False, maximize=False;
  * lightning_model.py:196-197): ONE launch updates every tensor of a table.

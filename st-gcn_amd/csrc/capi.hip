@@ -194,6 +194,17 @@ bool x_from_u(const stgcn_desc_t *d) {
     return fused_spb(d) || spatial_dx_prev_supported(d->N, d->C_in, d->T, d->V, d->K);
   return fold_spb(d) && !fold_bna(d) && d->K == 1 && gather_prev_supported(d->C_in, d->T, d->V);
 }
+// STGCN_PLAN_X_FROM_U_EVAL: the same input form in the eval forward (training ==
+// 0). BN1 and BN2 are per-channel constants there and no backward follows, so
+// only the forward kernels decide: the bf16 fused spatial forward stages
+// ReLU(BN2_prev(U_prev)) whatever the partition count, and any folded block that
+// forms G (V = 18 and V = 25) runs k_gather4 in prev mode where its blocks do
+// not cross a clip.
+bool x_from_u_eval(const stgcn_desc_t *d) {
+  if (d->training || residual(d)) return false;
+  if (fused_sp(d)) return true;
+  return fold_w(d) && !fold_bna(d) && gather_prev_supported(d->C_in, d->T, d->V);
+}
 
 // sum_{n,t} dZ of the non-residual block from per-tap sums of dU (clip-chunk
 // sums written by the ReLU + BN2 backward apply, k_fold_tq, one small GEMM with
@@ -741,6 +752,7 @@ int stgcn_block_plan(const stgcn_desc_t *d, uint32_t *plan) {
   if (f16x2_tw(d)) f |= STGCN_PLAN_F16X2;
   if (fold_bna(d)) f |= STGCN_PLAN_FOLD_NO_G;
   if (x_from_u(d)) f |= STGCN_PLAN_X_FROM_U;
+  if (x_from_u_eval(d)) f |= STGCN_PLAN_X_FROM_U_EVAL;
   *plan = f;
   return STGCN_OK;
 }
@@ -834,7 +846,9 @@ int stgcn_block_fwd(const stgcn_desc_t *d, const stgcn_fwd_args_t *a, void *work
   const bool xu = a && a->prev_U;
   const bool ystats_only = a && !a->y && a->y_stats && d->training && !res && a->dropout_p == 0.f;
   // ABI 9: y and y_stats both null: no output pass (stgcn_head_fwd_u pools from U)
-  const bool no_out = a && !a->y && !a->y_stats && d->training && !res && a->dropout_p == 0.f;
+  // (eval, non-residual: the same, U is the handoff -- dropout is inert there)
+  const bool no_out = a && !a->y && !a->y_stats && !res &&
+                      (d->training ? a->dropout_p == 0.f : true);
   if (!a || (!a->x && !xu) || !a->A || !a->W || !a->bW || !a->Wt || !a->bWt || !a->g1 ||
       !a->b1 || !a->g2 || !a->b2 || (!a->y && !ystats_only && !no_out) || !a->Z ||
       (!res && !a->U) ||
@@ -844,7 +858,9 @@ int stgcn_block_fwd(const stgcn_desc_t *d, const stgcn_fwd_args_t *a, void *work
     return fail(STGCN_E_INVALID, "residual block: null Za / projection weights");
   if (!a->rm1 || !a->rv1 || !a->rm2 || !a->rv2)
     return fail(STGCN_E_INVALID, "null running-stat buffer");
-  if (xu && (!x_from_u(d) || !a->x_stats || !a->prev_stats || !a->prev_g2 || !a->prev_b2 ||
+  // (eval, STGCN_PLAN_X_FROM_U_EVAL: BN1 takes the running statistics, no x_stats)
+  if (xu && (!(x_from_u(d) || x_from_u_eval(d)) || (d->training && !a->x_stats) ||
+             !a->prev_stats || !a->prev_g2 || !a->prev_b2 ||
              ((uintptr_t)a->prev_U & 15) != 0))
     return fail(STGCN_E_INVALID,
                 "prev_U input: needs STGCN_PLAN_X_FROM_U, x_stats, prev_stats / prev_g2 / "

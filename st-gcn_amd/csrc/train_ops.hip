@@ -160,12 +160,14 @@ __global__ __launch_bounds__(256) void k_head_pool_u(const float *U, const float
   if (lane == 0) pooled[row] = s / (float)L;
 }
 
-// one block per clip: logits = pooled W^T + b, per-clip CE loss (log-sum-exp)
-__global__ __launch_bounds__(256) void k_head_fc_ce(const float *pooled, const float *W,
-                                                    const float *bias, const int64_t *labels,
-                                                    float *logits, float *lossv, int C,
-                                                    int classes) {
-  extern __shared__ float sh[];  // [C] pooled row, [classes] logits, [8] reduction
+// The logits row of clip blockIdx.x and its log-sum-exp, shared by k_head_fc_ce
+// and k_head_eval_row (one function: the same instructions, so the evaluation
+// head's logits and losses are bit-identical to the training head's). sh:
+// [C] pooled row, [classes] logits (kept for the caller), [8] reduction. Every
+// thread returns the row maximum mx and the sum tot of exp(logit - mx).
+__device__ __forceinline__ void head_fc_lse(const float *pooled, const float *W,
+                                            const float *bias, float *logits, int C,
+                                            int classes, float *sh, float &mx, float &tot) {
   float *pr = sh, *lg = sh + C, *red = lg + classes;
   const int n = blockIdx.x, tid = threadIdx.x;
   for (int c = tid; c < C; c += 256) pr[c] = pooled[(int64_t)n * C + c];
@@ -179,7 +181,7 @@ __global__ __launch_bounds__(256) void k_head_fc_ce(const float *pooled, const f
     logits[(int64_t)n * classes + j] = a;
   }
   __syncthreads();
-  float mx = -INFINITY;
+  mx = -INFINITY;
   for (int j = tid; j < classes; j += 256) mx = fmaxf(mx, lg[j]);
   for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
   if ((tid & 63) == 0) red[tid >> 6] = mx;
@@ -191,11 +193,145 @@ __global__ __launch_bounds__(256) void k_head_fc_ce(const float *pooled, const f
   se = wave_sumf(se);
   if ((tid & 63) == 0) red[4 + (tid >> 6)] = se;
   __syncthreads();
-  if (tid == 0) {
-    const float tot = (red[4] + red[5]) + (red[6] + red[7]);
+  tot = (red[4] + red[5]) + (red[6] + red[7]);
+}
+
+// one block per clip: logits = pooled W^T + b, per-clip CE loss (log-sum-exp)
+__global__ __launch_bounds__(256) void k_head_fc_ce(const float *pooled, const float *W,
+                                                    const float *bias, const int64_t *labels,
+                                                    float *logits, float *lossv, int C,
+                                                    int classes) {
+  extern __shared__ float sh[];  // [C] pooled row, [classes] logits, [8] reduction
+  float mx, tot;
+  head_fc_lse(pooled, W, bias, logits, C, classes, sh, mx, tot);
+  if (threadIdx.x == 0) {
+    const float *lg = sh + C;
+    const int n = blockIdx.x;
     const int64_t y = labels[n];
     lossv[n] = (y >= 0 && y < classes) ? (logf(tot) + mx) - lg[y] : NAN;  // bad label: NaN
   }
+}
+
+// ---------------------------------------------------------------------------
+// Evaluation head (validation_step / test_step, lightning_model.py:213-253, and
+// compute_conf_mat :123-133): the same logits and per-clip loss, the predicted
+// class and the metrics of an epoch kept on the device.
+// ---------------------------------------------------------------------------
+// (value, index) maximum with ties going to the lowest index
+__device__ __forceinline__ void argmax_take(float &bv, int &bi, float v, int i) {
+  if (v > bv || (v == bv && i < bi)) {
+    bv = v;
+    bi = i;
+  }
+}
+
+// one block per clip: k_head_fc_ce's logits and loss (a label outside
+// [0, classes) is cross entropy's ignore_index: loss 0, the label indexes
+// nothing) and pred = the lowest index attaining the maximum logit, reduced as
+// (value, index) pairs over the lanes of each wave, then over the four waves
+__global__ __launch_bounds__(256) void k_head_eval_row(const float *pooled, const float *W,
+                                                       const float *bias, const int64_t *labels,
+                                                       float *logits, float *lossv, int32_t *pred,
+                                                       int C, int classes) {
+  extern __shared__ float sh[];  // [C] pooled row, [classes] logits, [8] reduction
+  float mx, tot;
+  head_fc_lse(pooled, W, bias, logits, C, classes, sh, mx, tot);
+  __syncthreads();  // (every thread has read the reduction words: the argmax reuses them)
+  const float *lg = sh + C;
+  float *av = sh + C + classes;  // [4] value, [4] index per wave
+  int *ai = reinterpret_cast<int *>(av + 4);
+  const int n = blockIdx.x, tid = threadIdx.x;
+  if (tid == 0) {
+    const int64_t y = labels[n];
+    lossv[n] = (y >= 0 && y < classes) ? (logf(tot) + mx) - lg[y] : 0.f;
+  }
+  float bv = -INFINITY;
+  int bi = INT32_MAX;
+  for (int j = tid; j < classes; j += 256) argmax_take(bv, bi, lg[j], j);
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(bv, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    argmax_take(bv, bi, ov, oi);
+  }
+  if ((tid & 63) == 0) {
+    av[tid >> 6] = bv;
+    ai[tid >> 6] = bi;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    for (int w = 1; w < 4; ++w) argmax_take(bv, bi, av[w], ai[w]);
+    pred[n] = bi < classes ? bi : 0;  // (no logit compares: every one NaN)
+  }
+}
+
+// The batch pass, ONE workgroup: loss = the mean of lossv over the clips with a
+// valid label (k_head_loss_mean's fixed-order fp64 sum, so the same bits when
+// every label is valid; 0 without a valid clip) and, metrics non-null, the
+// epoch's words and confusion matrix. Wave w takes clips w, w + 4, ..: its
+// lanes count the logits that rank before the label's (top-k hit: fewer than
+// topk of them). Counts are integers, the sums one fp64 add per word from
+// thread 0, the matrix integer atomics: the result does not depend on order.
+__global__ __launch_bounds__(256) void k_head_eval_batch(const float *logits,
+                                                         const int64_t *labels,
+                                                         const float *lossv,
+                                                         const int32_t *pred, float *loss,
+                                                         void *metrics, int N, int classes,
+                                                         int topk) {
+  __shared__ int cnt[4][4];  // per wave: valid, invalid, correct, top-k hits
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  unsigned long long *conf =
+      metrics ? reinterpret_cast<unsigned long long *>(metrics) + 8 : nullptr;
+  int valid = 0, invalid = 0, correct = 0, hits = 0;
+  for (int n = wave; n < N; n += 4) {
+    const int64_t y = labels[n];  // (wave-uniform)
+    if (y < 0 || y >= classes) {
+      ++invalid;
+      continue;
+    }
+    ++valid;
+    const int p = pred[n];
+    correct += p == (int)y ? 1 : 0;
+    if (!metrics) continue;
+    const float *lg = logits + (int64_t)n * classes;
+    const float ly = lg[y];
+    int before = 0;
+    for (int j = lane; j < classes; j += 64) {
+      const float v = lg[j];
+      before += (v > ly || (v == ly && j < (int)y)) ? 1 : 0;
+    }
+    for (int o = 32; o > 0; o >>= 1) before += __shfl_xor(before, o, 64);
+    hits += before < topk ? 1 : 0;
+    if (lane == 0) atomicAdd(conf + (size_t)y * classes + p, 1ull);
+  }
+  if (lane == 0) {
+    cnt[wave][0] = valid;
+    cnt[wave][1] = invalid;
+    cnt[wave][2] = correct;
+    cnt[wave][3] = hits;
+  }
+  __syncthreads();
+  if (tid != 0) return;
+  int64_t tot[4];
+  for (int i = 0; i < 4; ++i)
+    tot[i] = (int64_t)cnt[0][i] + cnt[1][i] + cnt[2][i] + cnt[3][i];
+  double s = 0.0;
+  for (int n = 0; n < N; ++n) {
+    const int64_t y = labels[n];
+    if (y >= 0 && y < classes) s += lossv[n];
+  }
+  const double mean = tot[0] > 0 ? s / (double)tot[0] : 0.0;
+  loss[0] = (float)mean;
+  if (!metrics) return;
+  int64_t *mi = reinterpret_cast<int64_t *>(metrics);
+  double *md = reinterpret_cast<double *>(metrics);
+  mi[0] += 1;
+  mi[1] += tot[0];
+  mi[2] += tot[2];
+  mi[3] += tot[3];
+  mi[4] += tot[1];
+  md[5] += s;
+  md[6] += mean;
+  md[7] += tot[0] > 0 ? (double)tot[2] / (double)tot[0] : 0.0;
 }
 
 // loss = mean_n lossv[n] (fixed order: deterministic)
@@ -393,6 +529,80 @@ int stgcn_head_fwd_u(const stgcn_head_desc_t *d, const float *U, const float *st
   hipLaunchKernelGGL(k_head_loss_mean, dim3(1), dim3(64), 0, s, lossv, loss, d->N);
   HIP_TRY2(hipGetLastError());
   return STGCN_OK;
+}
+
+int stgcn_features(void) { return STGCN_FEATURE_EVAL_CHAIN | STGCN_FEATURE_EVAL_HEAD; }
+
+// (classes of a metrics block: the head's own LDS limit at C = 1)
+static bool eval_classes_ok(int classes) {
+  return classes > 0 && (size_t)(1 + classes + 8) * sizeof(float) <= 64 * 1024;
+}
+
+size_t stgcn_eval_metrics_bytes(int classes) {
+  if (!eval_classes_ok(classes)) return 0;
+  return 8 * sizeof(int64_t) + (size_t)classes * classes * sizeof(int64_t);
+}
+
+int stgcn_eval_metrics_reset(void *metrics, int classes, void *stream) {
+  const size_t nbytes = stgcn_eval_metrics_bytes(classes);
+  if (!metrics || !nbytes) return fail(STGCN_E_INVALID, "eval metrics: null block or bad classes");
+  HIP_TRY2(hipMemsetAsync(metrics, 0, nbytes, (hipStream_t)stream));
+  return STGCN_OK;
+}
+
+// the checks of both forms of the evaluation head (src: y or U)
+static int head_eval_check(const stgcn_eval_desc_t *d, const void *src, const float *W,
+                           const float *bias, const int64_t *labels, const float *pooled,
+                           const float *logits, const float *lossv, const float *loss,
+                           const int32_t *pred) {
+  if (!d || d->N <= 0 || d->C <= 0 || d->L <= 0 || d->classes <= 0)
+    return fail(STGCN_E_INVALID, "head: bad descriptor");
+  if (d->topk < 1 || d->topk > d->classes)
+    return fail(STGCN_E_INVALID, "head: topk outside [1, classes]");
+  if (!src || !W || !bias || !labels || !pooled || !logits || !lossv || !loss || !pred)
+    return fail(STGCN_E_INVALID, "head: null tensor argument");
+  if ((size_t)(d->C + d->classes + 8) * sizeof(float) > 64 * 1024)
+    return fail(STGCN_E_UNSUPPORTED, "head: C + classes too large");
+  return STGCN_OK;
+}
+
+// logits, losses and predictions from pooled, then the batch pass
+static int head_eval_tail(const stgcn_eval_desc_t *d, const float *W, const float *bias,
+                          const int64_t *labels, float *pooled, float *logits, float *lossv,
+                          float *loss, int32_t *pred, void *metrics, hipStream_t s) {
+  hipLaunchKernelGGL(k_head_eval_row, dim3(d->N), dim3(256),
+                     (size_t)(d->C + d->classes + 8) * sizeof(float), s, pooled, W, bias, labels,
+                     logits, lossv, pred, d->C, d->classes);
+  hipLaunchKernelGGL(k_head_eval_batch, dim3(1), dim3(256), 0, s, logits, labels, lossv, pred,
+                     loss, metrics, d->N, d->classes, d->topk);
+  HIP_TRY2(hipGetLastError());
+  return STGCN_OK;
+}
+
+int stgcn_head_eval(const stgcn_eval_desc_t *d, const float *y, const float *W, const float *bias,
+                    const int64_t *labels, float *pooled, float *logits, float *lossv,
+                    float *loss, int32_t *pred, void *metrics, void *stream) {
+  int rc = head_eval_check(d, y, W, bias, labels, pooled, logits, lossv, loss, pred);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t rows = (int64_t)d->N * d->C;
+  hipLaunchKernelGGL(k_head_pool, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, y, pooled,
+                     rows, d->L);
+  return head_eval_tail(d, W, bias, labels, pooled, logits, lossv, loss, pred, metrics, s);
+}
+
+int stgcn_head_eval_u(const stgcn_eval_desc_t *d, const float *U, const float *stats2,
+                      const float *g2, const float *b2, const float *W, const float *bias,
+                      const int64_t *labels, float *pooled, float *logits, float *lossv,
+                      float *loss, int32_t *pred, void *metrics, void *stream) {
+  int rc = head_eval_check(d, U, W, bias, labels, pooled, logits, lossv, loss, pred);
+  if (rc) return rc;
+  if (!stats2 || !g2 || !b2) return fail(STGCN_E_INVALID, "head: null tensor argument");
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t rows = (int64_t)d->N * d->C;
+  hipLaunchKernelGGL(k_head_pool_u, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, U, stats2,
+                     stats2 + d->C, g2, b2, pooled, rows, d->C, d->L);
+  return head_eval_tail(d, W, bias, labels, pooled, logits, lossv, loss, pred, metrics, s);
 }
 
 int stgcn_head_bwd(const stgcn_head_desc_t *d, const float *pooled, const float *logits,

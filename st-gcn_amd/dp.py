@@ -29,6 +29,12 @@ The reference has no distributed code of its own (only
 PyTorch-Lightning's inherited Trainer flags could enable DDP); this is the
 MI355X-native counterpart of that DDP path. With ~2.7 M fp32 parameters
 (10.8 MB) per step the default 4 MB buckets give 3-4 collectives per step.
+
+Evaluation needs no gradient traffic: each rank runs ``STGCNStack.eval_step``
+on its shard into its own ``train_ops.EvalMetrics``, and the epoch's result is
+the plain sum over ranks of the block's words and matrix (integer counts and
+fp64 sums: one all-reduce(SUM) of ``metrics.buf`` viewed as int64 for words
+0-4 and the matrix, as float64 for words 5-7). Not built here.
 """
 import contextlib
 

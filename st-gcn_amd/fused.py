@@ -144,6 +144,102 @@ def lazy_links(blocks, x_shape):
     return out
 
 
+def eval_links(blocks, descs):
+    """Per block of a stack in eval (descs: its eval descriptors, stack_descs(...,
+    training=False)): "lazy" when its output stays unwritten -- a non-residual
+    block feeding a block whose eval forward forms ReLU(BN2(U)) on load
+    (STGCN_PLAN_X_FROM_U_EVAL), neither with forward hooks -- else "written";
+    the last block "head" when the scoring head can pool from its U
+    (non-residual, no hooks). No backward and no dropout condition applies."""
+    lib = hip_lib.lib()
+    out = []
+    for i, blk in enumerate(blocks):
+        if i + 1 == len(blocks):
+            out.append("head" if not blk.residual and not _hooked(blk) else "written")
+            continue
+        plan = ctypes.c_uint32(0)
+        hip_lib.check(lib.stgcn_block_plan(ctypes.byref(descs[i + 1]), ctypes.byref(plan)))
+        ok = (not blk.residual and not _hooked(blk) and not _hooked(blocks[i + 1])
+              and bool(plan.value & hip_lib.PLAN_X_FROM_U_EVAL))
+        out.append("lazy" if ok else "written")
+    return out
+
+
+def eval_forward(blocks, x, descs, links, preps):
+    """The forward of a block stack in eval with nothing kept for a backward
+    (model.STGCNStack.eval_step): x (N, C, T, V) -> ("y", y) with the last
+    block's output written, or ("u", (U, stats2, g2, b2)) with it left to the
+    head (links[-1] == "head"). descs / links / preps: stack_descs(...,
+    training=False), eval_links and the eval FoldPrep buffers. U and y ping-pong
+    between two buffers (a block's U goes to the one its input does not occupy,
+    a written y over that input, which every kernel before the output pass has
+    consumed; a residual block's y beside its input, which its last kernel still
+    reads); one Z (and Za) scratch and one workspace, sized to the largest block,
+    serve every block; G lives in the workspace. A block with forward hooks
+    runs through its module call, so the hooks fire and see written tensors."""
+    lib = hip_lib.lib()
+    dev = x.device
+    stream = hip_lib.stream_handle(dev)
+    hooked = [_hooked(b) for b in blocks]
+    own = [d for d, h in zip(descs, hooked) if not h]
+    f32 = dict(device=dev, dtype=torch.float32)
+    bufs, Z, Za, ws, nws = [None, None], None, None, None, 0
+    if own:
+        nout = max(d.N * d.C_out * d.T_out * d.V for d in own)
+        nz = max(d.N * d.C_out * d.T * d.V for d in own)
+        bufs = [torch.empty(nout, **f32), torch.empty(nout, **f32)]
+        Z = torch.empty(nz, **f32)
+        if any(b.residual and not h for b, h in zip(blocks, hooked)):
+            Za = torch.empty(nz, **f32)
+        sizes = [lib.stgcn_fwd_workspace_bytes(ctypes.byref(d)) for d in own]
+        if not all(sizes):
+            hip_lib.check(lib.stgcn_check_desc(ctypes.byref(own[sizes.index(0)])))
+        nws = max(sizes)
+        ws = torch.empty(nws, device=dev, dtype=torch.uint8)
+    cur, hold, prev = x, None, None  # input tensor (None: lazy), its buffer, previous (U, ...)
+    for blk, desc, link, prep, hk in zip(blocks, descs, links, preps, hooked):
+        if hk:  # (eval_links wrote both of its links)
+            cur, hold, prev = blk(cur), None, None
+            continue
+        if cur is not None:
+            cur = _f32c(cur.float().contiguous(), "x")
+        sc, tc, bn1, bn2 = blk.spatialConv, blk.temporalConv, blk.batch_n, blk.batch_n_2
+        params = (sc.A, sc.W.weight, sc.W.bias, tc.weight, tc.bias, bn1.weight, bn1.bias,
+                  bn2.weight, bn2.bias, bn1.running_mean, bn1.running_var, bn2.running_mean,
+                  bn2.running_var)
+        for t in params:
+            _f32c(t, "block parameter")
+        C_in, C_out = desc.C_in, desc.C_out
+        shape = (desc.N, C_out, desc.T_out, desc.V)
+        nel = shape[0] * shape[1] * shape[2] * shape[3]
+        iu = 0 if hold is None else 1 - hold
+        stats = torch.empty(2 * C_in + 2 * C_out, **f32)
+        Wr = br = U = y = None
+        if blk.residual:
+            proj = blk.apply_residual if isinstance(blk.apply_residual, torch.nn.Conv2d) else None
+            if proj is not None:
+                Wr, br = _f32c(proj.weight, "Wr"), _f32c(proj.bias, "br")
+            y = bufs[iu][:nel].view(shape)
+        else:
+            U = bufs[iu][:nel].view(shape)
+            if link == "written":
+                y = bufs[1 - iu][:nel].view(shape)
+        args = _args(hip_lib.FwdArgs, [hip_lib.ptr(t) for t in (
+            cur, *params, y, Z, U, stats, Wr, br, Za if blk.residual else None,
+            None, None, None)], 0.0, 0, prep=hip_lib.ptr(prep))
+        if cur is None:
+            pU, pstats, pg2, pb2 = prev
+            args.prev_U, args.prev_stats = hip_lib.ptr(pU), hip_lib.ptr(pstats)
+            args.prev_g2, args.prev_b2 = hip_lib.ptr(pg2), hip_lib.ptr(pb2)
+        hip_lib.check(lib.stgcn_block_fwd(ctypes.byref(desc), ctypes.byref(args), hip_lib.ptr(ws),
+                                          nws, stream))
+        if y is not None:
+            cur, hold, prev = y, (iu if blk.residual else 1 - iu), None
+        else:
+            cur, hold, prev = None, iu, (U, stats[2 * C_in:], bn2.weight, bn2.bias)
+    return ("y", cur) if cur is not None else ("u", prev)
+
+
 class FoldPrep:
     """The per-step weight preparation of a block stack's folded blocks (ABI 7
     stgcn_fold_prep: every folded block's Wc, bias table, max |Wc|, packed
@@ -156,12 +252,14 @@ class FoldPrep:
     def __init__(self):
         self._bufs = {}
 
-    def run(self, blocks, x_shape, dev):
+    def run(self, blocks, x_shape, dev, training=True):
         """blocks: the stack's SpatialTemporalConv modules in order; x_shape the
-        stack input (N, C, T, V). Returns one prep tensor (or None) per block."""
+        stack input (N, C, T, V). Returns one prep tensor (or None) per block.
+        training: the descriptors the buffers are formed for (an eval step keeps
+        a FoldPrep of its own, so the two never share a buffer)."""
         lib = hip_lib.lib()
         descs, weights, ptrs, out = [], [], [], []
-        for i, (blk, desc) in enumerate(zip(blocks, stack_descs(blocks, x_shape))):
+        for i, (blk, desc) in enumerate(zip(blocks, stack_descs(blocks, x_shape, training))):
             sc, tc = blk.spatialConv, blk.temporalConv
             gemm = blk.gemm_mode()
             nbytes = lib.stgcn_fold_prep_bytes(ctypes.byref(desc))
@@ -170,7 +268,7 @@ class FoldPrep:
                 # (the contents depend on the weights and (C, T, V) only: keyed
                 # without the batch, one buffer per block, replaced when the
                 # shape changes -- a ragged last batch reuses it)
-                key = (tuple(x_shape[1:]), gemm, nbytes, dev)
+                key = (tuple(x_shape[1:]), gemm, nbytes, dev, bool(training))
                 held = self._bufs.get(i)
                 buf = held[1] if held is not None and held[0] == key else None
                 if buf is None:

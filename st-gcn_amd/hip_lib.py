@@ -32,6 +32,10 @@ PLAN_FOLD, PLAN_SP_FWD_FUSED, PLAN_SP_BWD_FUSED, PLAN_ACT_BF16 = 1, 2, 4, 8
 PLAN_WSP_SPLIT, PLAN_TCONV_SPLIT, PLAN_TWGRAD_SPLIT, PLAN_F16X2 = 16, 32, 64, 128
 PLAN_FOLD_NO_G = 256
 PLAN_X_FROM_U = 512  # ABI 8: the input as ReLU(BN2(U)) of the previous block
+PLAN_X_FROM_U_EVAL = 1024  # ... in the eval forward (stgcn_features: FEATURE_EVAL_CHAIN)
+# stgcn_features bits: additions within ABI 11
+FEATURE_EVAL_CHAIN, FEATURE_EVAL_HEAD = 1, 2
+METRICS_WORDS = 8  # 8-byte words of a metrics block before its confusion matrix
 # ABI 7: a y_stats / x_stats block: 5 * C doubles, then STATS_AMAX_WORDS uint32 (max |y|)
 STATS_AMAX_WORDS = 2048
 
@@ -92,6 +96,11 @@ class HeadDesc(ctypes.Structure):  # ABI 3
     _fields_ = [("N", _c_int), ("C", _c_int), ("L", _c_int), ("classes", _c_int)]
 
 
+class EvalDesc(ctypes.Structure):  # stgcn_head_eval (FEATURE_EVAL_HEAD)
+    _fields_ = [("N", _c_int), ("C", _c_int), ("L", _c_int), ("classes", _c_int),
+                ("topk", _c_int)]
+
+
 class AdamTensor(ctypes.Structure):  # ABI 3
     _fields_ = [("param", _vp), ("grad", _vp), ("exp_avg", _vp), ("exp_avg_sq", _vp),
                 ("numel", ctypes.c_int64)]
@@ -105,7 +114,9 @@ EXPORTED = ("stgcn_abi_version", "stgcn_last_error", "stgcn_check_desc",
             "stgcn_adam_build_table", "stgcn_adam_step", "stgcn_spatial_workspace_bytes",
             "stgcn_spatial_fwd", "stgcn_spatial_bwd", "stgcn_keep_g_bytes",
             "stgcn_block_plan", "stgcn_fold_prep_bytes", "stgcn_fold_prep", "stgcn_head_fwd_u",
-            "stgcn_head_bwd_nc", "stgcn_adam_step_dev")
+            "stgcn_head_bwd_nc", "stgcn_adam_step_dev", "stgcn_features",
+            "stgcn_eval_metrics_bytes", "stgcn_eval_metrics_reset", "stgcn_head_eval",
+            "stgcn_head_eval_u")
 
 _LIB = None
 
@@ -145,6 +156,15 @@ def load_library(path=LIB_PATH):
     lib.stgcn_head_bwd.restype = ctypes.c_int
     lib.stgcn_head_bwd_nc.argtypes = [ctypes.POINTER(HeadDesc)] + [_vp] * 10 + [_vp]
     lib.stgcn_head_bwd_nc.restype = ctypes.c_int
+    lib.stgcn_features.restype = ctypes.c_int
+    lib.stgcn_eval_metrics_bytes.argtypes = [ctypes.c_int]
+    lib.stgcn_eval_metrics_bytes.restype = ctypes.c_size_t
+    lib.stgcn_eval_metrics_reset.argtypes = [_vp, ctypes.c_int, _vp]
+    lib.stgcn_eval_metrics_reset.restype = ctypes.c_int
+    lib.stgcn_head_eval.argtypes = [ctypes.POINTER(EvalDesc)] + [_vp] * 10 + [_vp]
+    lib.stgcn_head_eval.restype = ctypes.c_int
+    lib.stgcn_head_eval_u.argtypes = [ctypes.POINTER(EvalDesc)] + [_vp] * 13 + [_vp]
+    lib.stgcn_head_eval_u.restype = ctypes.c_int
     lib.stgcn_adam_table_bytes.argtypes = [ctypes.c_int]
     lib.stgcn_adam_table_bytes.restype = ctypes.c_size_t
     lib.stgcn_adam_build_table.argtypes = [ctypes.POINTER(AdamTensor), ctypes.c_int, _vp,

@@ -8,9 +8,10 @@ import torch
 import torch.nn as nn
 
 from .graph import Strategy, get_normalized_adjacency_matrices
-from .fused import FoldPrep, head_link_ok, lazy_links
+from .fused import (FoldPrep, eval_forward, eval_links, head_link_ok, lazy_links,
+                    stack_descs)
 from .network import SpatialTemporalConv, StackChain
-from .train_ops import StgcnHeadFn
+from .train_ops import EvalMetrics, StgcnHeadFn, head_eval
 
 # (C_out, temporal stride) per block, lightning_model.py:65-86.
 LAYERS = [(64, 1), (64, 1), (64, 1), (64, 1), (128, 2), (128, 1), (128, 1),
@@ -110,6 +111,63 @@ class STGCNStack(nn.Module):
                 return StgcnHeadFn.apply(x, self.fc_layer.weight, self.fc_layer.bias, labels,
                                          (U, stats2) + tuple(chain.g2b2))
         return StgcnHeadFn.apply(x, self.fc_layer.weight, self.fc_layer.bias, labels)
+
+    @torch.no_grad()
+    def eval_step(self, x, labels, metrics=None):
+        """The forward-only step of validation_step / test_step
+        (lightning_model.py:213-253): x (N, C_in, T, V) NCTV, labels int64 (N) ->
+        (mean cross-entropy loss, logits), the values of
+        ``F.cross_entropy(self.forward_nctv(x), labels)`` in eval mode. metrics:
+        a ``train_ops.EvalMetrics`` that takes the batch's counts, sums and
+        confusion matrix on the device. No host read of a device value, so the
+        call is replay-safe under ``train_ops.GraphedStep`` with static inputs.
+        Nothing is kept for a backward: the blocks chain through their U (a
+        block's output stays unwritten where the next block's eval forward forms
+        ReLU(BN2(U)) on load, the last one's where the head pools from U), two
+        ping-pong buffers and one Z scratch serve the stack, and the folded
+        blocks' weight operands are formed once per call. ``last_eval_plan``
+        then lists "lazy" / "written" per link and "head" / "written" last."""
+        if self.training:
+            raise RuntimeError("eval_step: the module is in training mode (call .eval())")
+        if not x.is_cuda or x.dim() != 4:
+            raise RuntimeError("eval_step: expected a (N, C, T, V) GPU tensor")
+        x = x.float().contiguous()
+        blocks = list(self.conv)
+        descs = stack_descs(blocks, tuple(x.shape), training=False)
+        links = eval_links(blocks, descs)
+        # (formed per call: FusedAdam updates the weights through raw pointers, so
+        # no tensor version says whether they changed; a FoldPrep apart from the
+        # training step's, so the two never share a buffer)
+        if getattr(self, "_fold_prep_eval", None) is None:
+            self._fold_prep_eval = FoldPrep()
+        preps = self._fold_prep_eval.run(blocks, tuple(x.shape), x.device, training=False)
+        kind, out = eval_forward(blocks, x, descs, links, preps)
+        self.last_eval_plan = links
+        W, b = self.fc_layer.weight, self.fc_layer.bias
+        if kind == "u":
+            loss, logits, _, _ = head_eval(None, W, b, labels, metrics=metrics, from_u=out)
+        else:
+            loss, logits, _, _ = head_eval(out, W, b, labels, metrics=metrics)
+        return loss, logits
+
+    def compute_accuracy(self, pred, gt):
+        """pred: model output (N, nr_classes), gt: categorical labels -> the
+        fraction of correct arg-max predictions as a host float
+        (lightning_model.py:114-121; the softmax there does not move the arg-max)."""
+        return (torch.argmax(pred, dim=1) == gt).sum().item() / len(pred)
+
+    def compute_conf_mat(self, dataloader):
+        """The confusion matrix of lightning_model.py:123-133 (int64 CPU tensor,
+        confusion[label][pred]) over batches (x (N, T, V, C_in), y) of a
+        dataloader, through ``eval_step`` and ``EvalMetrics``: counted on the
+        device, one copy to the host at the end."""
+        if self.training:
+            raise RuntimeError("compute_conf_mat: the module is in training mode (call .eval())")
+        dev = self.fc_layer.weight.device
+        metrics = EvalMetrics(self.nr_classes, device=dev)
+        for x, y in dataloader:
+            self.eval_step(x.to(dev).permute(0, 3, 1, 2), y.to(dev), metrics)
+        return metrics.result()["confusion"]
 
 
 class STGCN(nn.Module):

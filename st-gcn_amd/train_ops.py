@@ -95,6 +95,118 @@ class StgcnHeadFn(torch.autograd.Function):
         return dy, dW, db, None, None
 
 
+def decode_eval_metrics(buf, classes):
+    """The dict of a metrics block (stgcn_hip.h, stgcn_head_eval): ``buf`` its
+    bytes as a CPU uint8 tensor. batches, clips (with a valid label), invalid,
+    correct, topk_hits; loss / acc / topk_acc per clip; val_loss / val_acc the
+    mean of the batch means (validation_epoch_end, lightning_model.py:220-224,
+    which differs from the per-clip mean when the last batch is short);
+    confusion[label][pred] (int64, classes x classes; compute_conf_mat :123-133).
+    Pure host code: no GPU, no library."""
+    head = hip_lib.METRICS_WORDS * 8
+    nbytes = head + 8 * classes * classes
+    if buf.dtype != torch.uint8 or buf.is_cuda or buf.numel() != nbytes:
+        raise ValueError(f"metrics block: expected {nbytes} CPU uint8 bytes for {classes} classes")
+    buf = buf.contiguous().clone()
+    ints = buf[:head].view(torch.int64).tolist()
+    dbls = buf[:head].view(torch.float64).tolist()
+    batches, clips, correct, hits, invalid = ints[:5]
+    sum_loss, sum_batch_loss, sum_batch_acc = dbls[5:8]
+
+    def over(a, b):
+        return a / b if b else 0.0
+
+    return {"batches": batches, "clips": clips, "invalid": invalid, "correct": correct,
+            "topk_hits": hits, "loss": over(sum_loss, clips), "acc": over(correct, clips),
+            "topk_acc": over(hits, clips), "val_loss": over(sum_batch_loss, batches),
+            "val_acc": over(sum_batch_acc, batches),
+            "confusion": buf[head:].view(torch.int64).reshape(classes, classes).clone()}
+
+
+class EvalMetrics:
+    """The metrics of an evaluation epoch, accumulated on the device by
+    ``head_eval`` (stgcn_head_eval): counts, loss and accuracy sums and the
+    confusion matrix. No host read until ``result()``, which makes one
+    device-to-host copy, so an evaluation step can be captured in a HIP graph
+    (``GraphedStep``). ``topk``: the k of the top-k hit count."""
+
+    def __init__(self, classes, topk=1, device="cuda", buf=None):
+        """buf: a caller's uint8 device tensor of stgcn_eval_metrics_bytes(classes)
+        bytes to use as the block (reset here like an own one)."""
+        lib = hip_lib.lib()
+        nbytes = lib.stgcn_eval_metrics_bytes(int(classes))
+        if not nbytes:
+            raise ValueError(f"EvalMetrics: unsupported number of classes {classes}")
+        if not 1 <= topk <= classes:
+            raise ValueError("EvalMetrics: topk must be in [1, classes]")
+        self.classes, self.topk = int(classes), int(topk)
+        if buf is None:
+            buf = torch.empty(nbytes, device=device, dtype=torch.uint8)
+        elif (buf.dtype != torch.uint8 or not buf.is_cuda or not buf.is_contiguous()
+              or buf.numel() != nbytes or buf.data_ptr() % 8):
+            raise ValueError(f"EvalMetrics: buf must be {nbytes} contiguous, 8-byte aligned "
+                             "uint8 bytes on the GPU")
+        self.buf = buf
+        self.reset()
+
+    def reset(self):
+        hip_lib.check(hip_lib.lib().stgcn_eval_metrics_reset(
+            hip_lib.ptr(self.buf), self.classes, hip_lib.stream_handle(self.buf.device)))
+
+    def result(self):
+        return decode_eval_metrics(self.buf.cpu(), self.classes)
+
+
+def head_eval(y, W, b, labels, topk=1, metrics=None, from_u=None):
+    """The head of an evaluation step (stgcn_head_eval / stgcn_head_eval_u): y
+    (N, C, T, V), W (classes, C), b (classes), labels int64 (N) -> (loss, logits
+    (N, classes), pred int32 (N), lossv (N) the per-clip losses), with ``StgcnHeadFn``'s logits and loss bit for
+    bit when every label is valid; a label outside [0, classes) is ignored as
+    F.cross_entropy's ignore_index. metrics: an ``EvalMetrics`` that takes the
+    batch (its topk then applies). from_u = (U, stats2, g2, b2): y is None and the
+    pool forms ReLU(BN2(U)) on load. No autograd, no host read."""
+    lib = hip_lib.lib()
+    src = y if from_u is None else from_u[0]
+    if from_u is None:
+        src = src.contiguous()
+    for t, n in ((src, "y" if from_u is None else "U"), (W, "W"), (b, "b")):
+        _check_f32(t, n)
+    if labels.dtype != torch.int64 or not labels.is_cuda:
+        raise RuntimeError("labels: expected an int64 GPU tensor")
+    labels = labels.contiguous()
+    N, C = src.shape[0], src.shape[1]
+    L = src[0, 0].numel()
+    classes = W.shape[0]
+    if W.shape[1] != C or b.shape[0] != classes or labels.shape[0] != N:
+        raise RuntimeError("head: shape mismatch between y, W, b and labels")
+    mbuf = None
+    if metrics is not None:
+        if metrics.classes != classes or metrics.buf.device != src.device:
+            raise RuntimeError("head: the metrics block is for other classes or another device")
+        topk, mbuf = metrics.topk, metrics.buf
+    d = hip_lib.EvalDesc(N, C, L, classes, int(topk))
+    dev = src.device
+    pooled = torch.empty((N, C), device=dev, dtype=torch.float32)
+    logits = torch.empty((N, classes), device=dev, dtype=torch.float32)
+    lossv = torch.empty(N, device=dev, dtype=torch.float32)
+    loss = torch.empty((), device=dev, dtype=torch.float32)
+    pred = torch.empty(N, device=dev, dtype=torch.int32)
+    if from_u is not None:
+        U, stats2, g2, b2 = from_u
+        for t, n in ((stats2, "stats2"), (g2, "g2"), (b2, "b2")):
+            _check_f32(t, n)
+        if stats2.numel() < 2 * C or g2.numel() != C or b2.numel() != C:
+            raise RuntimeError("head: BN2 parameters do not match U")
+        hip_lib.check(lib.stgcn_head_eval_u(ctypes.byref(d), *[hip_lib.ptr(t) for t in (
+            U, stats2, g2, b2, W, b, labels, pooled, logits, lossv, loss, pred, mbuf)],
+            hip_lib.stream_handle(dev)))
+    else:
+        hip_lib.check(lib.stgcn_head_eval(ctypes.byref(d), *[hip_lib.ptr(t) for t in (
+            src, W, b, labels, pooled, logits, lossv, loss, pred, mbuf)],
+            hip_lib.stream_handle(dev)))
+    return loss, logits, pred, lossv
+
+
 class FusedAdam(torch.optim.Optimizer):
     """torch.optim.Adam (amsgrad=False, maximize=False, fp32 parameters on one
     device) with the update as one libstgcn_hip launch per step. The tensor
