@@ -32,6 +32,28 @@
  * Conventions
  *   - All tensors are caller-owned, contiguous, fp32, device memory, layout
  *     NCTV (N clips, C channels, T frames, V joints) as in the reference.
+ *   - Alignment. Every pointer either works at the alignment stated here or the
+ *     call returns STGCN_E_INVALID, naming the argument in stgcn_last_error(),
+ *     before its first launch (null optional arguments pass):
+ *       stgcn_block_fwd / stgcn_block_bwd / stgcn_fold_prep: every tensor, saved
+ *         buffer (Z, U, Za, stats, kept G, prep), chaining block (x_stats,
+ *         y_stats, dy_sums, prev_sums, dx_coef, dy_coef, prev_U, prev_g2,
+ *         prev_b2, dy_nc), gradient and the workspace: 16 bytes (the kernels move
+ *         them in 16-byte units; the opaque formats do not depend on pointer
+ *         values). Exceptions, taken at 4 bytes: the running statistics rm1, rv1,
+ *         rm2, rv2 (read and updated in place, one element at a time) and
+ *         prev_stats (the previous block's stats + 2 * C_in). dx without need_dx
+ *         and U of a residual block are ignored.
+ *       stgcn_spatial_fwd / stgcn_spatial_bwd: out, dx, dA, dW, dbW and the
+ *         workspace 16 bytes; x, A, W, bW, dout 4 bytes on the fp32 path (a
+ *         misaligned x or dout selects narrower kernels: slower, same results
+ *         to rounding), 16 bytes under STGCN_F_BF16.
+ *       stgcn_head_*: fp32 / int32 tensors 4 bytes, labels and the metrics block
+ *         8; stgcn_adam_*: the device table 8, every param / grad / exp_avg /
+ *         exp_avg_sq and the device step 4 (views into a flat bucket work in
+ *         place). These kernels access one element at a time.
+ *     A caller with a misaligned read-only input for a 16-byte argument passes an
+ *     aligned copy (the Python binding does); torch.empty results are aligned.
  *   - A is (K,V,V), W is (K*C_out, C_in) (the reference's 1x1 Conv2d weight),
  *     Wt is (C_out, C_out, 9) (the (9,1) Conv2d weight).
  *   - The workspace is caller-allocated (query *_workspace_bytes first); the

@@ -18,6 +18,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -49,6 +50,22 @@ namespace {
     if (e_ != hipSuccess)                                                                  \
       return fail(STGCN_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));        \
   } while (0)
+
+// The alignment contract of stgcn_hip.h (Conventions): the first pointer of the
+// list that is off `align` bytes fails the call, by name, before any launch.
+// Null pointers pass (optional arguments; the null checks come first).
+struct NamedPtr {
+  const void *p;
+  const char *name;
+};
+int check_aligned(std::initializer_list<NamedPtr> ptrs, unsigned align) {
+  for (const NamedPtr &q : ptrs)
+    if (((uintptr_t)q.p & (align - 1)) != 0)
+      return fail(STGCN_E_INVALID,
+                  std::string(q.name) + ": must be " + std::to_string(align) + "-byte aligned");
+  return STGCN_OK;
+}
+#define STGCN_P(s, m) NamedPtr{(s)->m, #m}
 
 size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 // bytes of a y_stats / x_stats block (ABI 7): 5 * C doubles of sums, then the
@@ -791,6 +808,11 @@ int stgcn_fold_prep(int nblocks, const stgcn_desc_t *descs, const stgcn_fold_wei
     const stgcn_fold_weights_t &w = weights[i];
     if (!prep[i] || !w.A || !w.W || !w.bW || !w.Wt || !w.bWt)
       return fail(STGCN_E_INVALID, "null fold_prep weights / buffer of a folded block");
+    if ((rc = check_aligned({NamedPtr{w.A, "A"}, NamedPtr{w.W, "W"}, NamedPtr{w.bW, "bW"},
+                             NamedPtr{w.Wt, "Wt"}, NamedPtr{w.bWt, "bWt"},
+                             NamedPtr{prep[i], "prep"}},
+                            16)))
+      return rc;
     const PrepLayout P = prep_layout(d, prep[i]);
     FoldPrepSpec b{};
     b.A = w.A;
@@ -865,6 +887,21 @@ int stgcn_block_fwd(const stgcn_desc_t *d, const stgcn_fwd_args_t *a, void *work
     return fail(STGCN_E_INVALID,
                 "prev_U input: needs STGCN_PLAN_X_FROM_U, x_stats, prev_stats / prev_g2 / "
                 "prev_b2 and a 16-byte aligned prev_U");
+  // the alignment contract (stgcn_hip.h): 16 bytes, but 4 for the running
+  // statistics (updated in place by scalar accesses, k_bn_finalize[_parts]) and
+  // for prev_stats (the previous block's stats + 2 * C_in_prev by construction)
+  if ((rc = check_aligned(
+           {STGCN_P(a, x), STGCN_P(a, A), STGCN_P(a, W), STGCN_P(a, bW), STGCN_P(a, Wt),
+            STGCN_P(a, bWt), STGCN_P(a, g1), STGCN_P(a, b1), STGCN_P(a, g2), STGCN_P(a, b2),
+            STGCN_P(a, y), STGCN_P(a, Z), NamedPtr{res ? nullptr : a->U, "U"}, STGCN_P(a, stats),
+            STGCN_P(a, Wr), STGCN_P(a, br), STGCN_P(a, Za), STGCN_P(a, G), STGCN_P(a, x_stats),
+            STGCN_P(a, y_stats), STGCN_P(a, prep), STGCN_P(a, prev_U), STGCN_P(a, prev_g2),
+            STGCN_P(a, prev_b2), NamedPtr{workspace, "workspace"}},
+           16)) ||
+      (rc = check_aligned({STGCN_P(a, rm1), STGCN_P(a, rv1), STGCN_P(a, rm2), STGCN_P(a, rv2),
+                           STGCN_P(a, prev_stats)},
+                          4)))
+    return rc;
   const FwdLayout L = fwd_layout(d, workspace);
   if (!workspace || workspace_bytes < L.total)
     return fail(STGCN_E_INVALID, "workspace too small");
@@ -1112,6 +1149,23 @@ int stgcn_block_bwd(const stgcn_desc_t *d, const stgcn_bwd_args_t *a, void *work
     return fail(STGCN_E_INVALID, "stack chaining applies to training mode only");
   if (a->dy_coef && (!a->dy_sums || res || drop.thresh))
     return fail(STGCN_E_INVALID, "dy_coef needs dy_sums, a non-residual block, no dropout");
+  // the alignment contract (stgcn_hip.h): 16 bytes, 4 for prev_stats. With x and
+  // prev_U aligned, the deferred-dx decision below (spatial_dx_prev_supported,
+  // which assumes aligned pointers) and the launch agree.
+  if ((rc = check_aligned(
+           {STGCN_P(a, dy), STGCN_P(a, x), STGCN_P(a, Z), NamedPtr{res ? nullptr : a->U, "U"},
+            STGCN_P(a, stats), STGCN_P(a, A), STGCN_P(a, W), STGCN_P(a, bW), STGCN_P(a, Wt),
+            STGCN_P(a, g1), STGCN_P(a, b1), STGCN_P(a, g2), STGCN_P(a, b2),
+            NamedPtr{d->need_dx ? a->dx : nullptr, "dx"}, STGCN_P(a, dA), STGCN_P(a, dW),
+            STGCN_P(a, dbW), STGCN_P(a, dWt), STGCN_P(a, dbWt), STGCN_P(a, dg1), STGCN_P(a, db1),
+            STGCN_P(a, dg2), STGCN_P(a, db2), STGCN_P(a, Wr), STGCN_P(a, Za), STGCN_P(a, y),
+            STGCN_P(a, dWr), STGCN_P(a, dbr), STGCN_P(a, G), STGCN_P(a, dy_sums),
+            STGCN_P(a, prev_g2), STGCN_P(a, prev_b2), STGCN_P(a, prev_sums), STGCN_P(a, prev_U),
+            STGCN_P(a, x_stats), STGCN_P(a, dx_coef), STGCN_P(a, dy_coef), STGCN_P(a, prep),
+            STGCN_P(a, dy_nc), NamedPtr{workspace, "workspace"}},
+           16)) ||
+      (rc = check_aligned({STGCN_P(a, prev_stats)}, 4)))
+    return rc;
   const BwdLayout L = bwd_layout(d, workspace);
   if (!workspace || workspace_bytes < L.total)
     return fail(STGCN_E_INVALID, "workspace too small");
@@ -2021,6 +2075,13 @@ int stgcn_spatial_fwd(const stgcn_spatial_desc_t *sd, const float *x, const floa
   if (rc) return rc;
   const stgcn_desc_t *d = &dd;
   if (!x || !A || !W || !bW || !out) return fail(STGCN_E_INVALID, "null tensor argument");
+  // the alignment contract (stgcn_hip.h): the fp32 path reads x, A, W, bW at their
+  // natural alignment (a misaligned x takes k_gather3 / k_gather_fwd, the rest is
+  // read one element at a time); the bf16 kernels are given 16 bytes throughout
+  if ((rc = check_aligned({NamedPtr{x, "x"}, NamedPtr{A, "A"}, NamedPtr{W, "W"}, NamedPtr{bW, "bW"}},
+                          bf16(d) ? 16 : 4)) ||
+      (rc = check_aligned({NamedPtr{out, "out"}, NamedPtr{workspace, "workspace"}}, 16)))
+    return rc;
   const SpatialLayout L = spatial_layout(d, workspace, false);
   if (!workspace || workspace_bytes < L.total) return fail(STGCN_E_INVALID, "workspace too small");
   hipStream_t s = (hipStream_t)stream;
@@ -2069,6 +2130,16 @@ int stgcn_spatial_bwd(const stgcn_spatial_desc_t *sd, const float *dout, const f
   const stgcn_desc_t *d = &dd;
   if (!dout || !x || !A || !W || !bW || !dA || !dW || !dbW)
     return fail(STGCN_E_INVALID, "null tensor argument");
+  // (as stgcn_spatial_fwd; a misaligned dout takes k_sum_nt, the 4-byte staging of
+  // k_wgrad_sp and the 4-byte input DMA of the H GEMM, a misaligned x k_gather3 and
+  // k_spatial_bwd3 / k_spatial_dx)
+  if ((rc = check_aligned({NamedPtr{dout, "dout"}, NamedPtr{x, "x"}, NamedPtr{A, "A"},
+                           NamedPtr{W, "W"}, NamedPtr{bW, "bW"}},
+                          bf16(d) ? 16 : 4)) ||
+      (rc = check_aligned({NamedPtr{dx, "dx"}, NamedPtr{dA, "dA"}, NamedPtr{dW, "dW"},
+                           NamedPtr{dbW, "dbW"}, NamedPtr{workspace, "workspace"}},
+                          16)))
+    return rc;
   const SpatialLayout L = spatial_layout(d, workspace, true);
   if (!workspace || workspace_bytes < L.total) return fail(STGCN_E_INVALID, "workspace too small");
   hipStream_t s = (hipStream_t)stream;

@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 
 #include "../../include/stgcn_hip.h"
@@ -26,6 +27,23 @@ int fail(int code, const std::string &m) {
   stgcn::set_last_error(m);
   return code;
 }
+
+// The alignment contract of stgcn_hip.h (Conventions) for the head and Adam:
+// every kernel below reads and writes one element at a time, so a pointer needs
+// its element's own alignment only (4 bytes fp32 / int32, 8 bytes int64 labels,
+// the metrics block and the Adam table). Null pointers pass.
+struct NamedPtr {
+  const void *p;
+  const char *name;
+};
+int check_aligned(std::initializer_list<NamedPtr> ptrs, unsigned align) {
+  for (const NamedPtr &q : ptrs)
+    if (((uintptr_t)q.p & (align - 1)) != 0)
+      return fail(STGCN_E_INVALID,
+                  std::string(q.name) + ": must be " + std::to_string(align) + "-byte aligned");
+  return STGCN_OK;
+}
+#define NP(v) NamedPtr{v, #v}
 
 #define HIP_TRY2(expr)                                                                     \
   do {                                                                                     \
@@ -437,6 +455,11 @@ int stgcn_adam_build_table(const stgcn_adam_tensor_t *tensors, int ntensors, voi
     if (!t.param || !t.grad || !t.exp_avg || !t.exp_avg_sq || t.numel <= 0)
       return fail(STGCN_E_INVALID,
                   "adam: tensor " + std::to_string(i) + " has a null pointer or numel <= 0");
+    if ((((uintptr_t)t.param | (uintptr_t)t.grad | (uintptr_t)t.exp_avg |
+          (uintptr_t)t.exp_avg_sq) & 3) != 0)
+      return fail(STGCN_E_INVALID,
+                  "adam: tensor " + std::to_string(i) + ": param / grad / exp_avg / exp_avg_sq "
+                  "must be 4-byte aligned");
     tab[i] = t;
     cs[i] = chunks;
     chunks += (t.numel + kAdamChunk - 1) / kAdamChunk;
@@ -452,6 +475,7 @@ int stgcn_adam_step(const void *dev_table, int ntensors, int64_t total_chunks, d
                     void *stream) {
   if (!dev_table || ntensors <= 0 || total_chunks <= 0 || step <= 0)
     return fail(STGCN_E_INVALID, "adam: bad table / chunk count / step");
+  if (int rc = check_aligned({NP(dev_table)}, 8)) return rc;
   // scalars as torch forms them: Python doubles, rounded to float at the kernel
   const double bc1 = 1.0 - std::pow(beta1, (double)step);
   const double bc2 = 1.0 - std::pow(beta2, (double)step);
@@ -477,6 +501,8 @@ int stgcn_adam_step_dev(const void *dev_table, int ntensors, int64_t total_chunk
                         void *stream) {
   if (!dev_table || ntensors <= 0 || total_chunks <= 0 || !step)
     return fail(STGCN_E_INVALID, "adam: bad table / chunk count / step pointer");
+  if (int rc = check_aligned({NP(dev_table)}, 8)) return rc;
+  if (int rc = check_aligned({NP(step)}, 4)) return rc;
   const auto *tab = reinterpret_cast<const stgcn_adam_tensor_t *>(dev_table);
   const auto *cs = reinterpret_cast<const int64_t *>(reinterpret_cast<const char *>(dev_table) +
                                                      (size_t)ntensors * sizeof(stgcn_adam_tensor_t));
@@ -494,6 +520,9 @@ int stgcn_head_fwd(const stgcn_head_desc_t *d, const float *y, const float *W, c
     return fail(STGCN_E_INVALID, "head: bad descriptor");
   if (!y || !W || !bias || !labels || !pooled || !logits || !lossv || !loss)
     return fail(STGCN_E_INVALID, "head: null tensor argument");
+  if (int rc = check_aligned({NP(y), NP(W), NP(bias), NP(pooled), NP(logits), NP(lossv), NP(loss)}, 4))
+    return rc;
+  if (int rc = check_aligned({NP(labels)}, 8)) return rc;
   if ((size_t)(d->C + d->classes + 8) * sizeof(float) > 64 * 1024)
     return fail(STGCN_E_UNSUPPORTED, "head: C + classes too large");
   hipStream_t s = (hipStream_t)stream;
@@ -517,6 +546,11 @@ int stgcn_head_fwd_u(const stgcn_head_desc_t *d, const float *U, const float *st
   if (!U || !stats2 || !g2 || !b2 || !W || !bias || !labels || !pooled || !logits || !lossv ||
       !loss)
     return fail(STGCN_E_INVALID, "head: null tensor argument");
+  if (int rc = check_aligned({NP(U), NP(stats2), NP(g2), NP(b2), NP(W), NP(bias), NP(pooled),
+                              NP(logits), NP(lossv), NP(loss)},
+                             4))
+    return rc;
+  if (int rc = check_aligned({NP(labels)}, 8)) return rc;
   if ((size_t)(d->C + d->classes + 8) * sizeof(float) > 64 * 1024)
     return fail(STGCN_E_UNSUPPORTED, "head: C + classes too large");
   hipStream_t s = (hipStream_t)stream;
@@ -546,6 +580,7 @@ size_t stgcn_eval_metrics_bytes(int classes) {
 int stgcn_eval_metrics_reset(void *metrics, int classes, void *stream) {
   const size_t nbytes = stgcn_eval_metrics_bytes(classes);
   if (!metrics || !nbytes) return fail(STGCN_E_INVALID, "eval metrics: null block or bad classes");
+  if (int rc = check_aligned({NP(metrics)}, 8)) return rc;
   HIP_TRY2(hipMemsetAsync(metrics, 0, nbytes, (hipStream_t)stream));
   return STGCN_OK;
 }
@@ -561,6 +596,15 @@ static int head_eval_check(const stgcn_eval_desc_t *d, const void *src, const fl
     return fail(STGCN_E_INVALID, "head: topk outside [1, classes]");
   if (!src || !W || !bias || !labels || !pooled || !logits || !lossv || !loss || !pred)
     return fail(STGCN_E_INVALID, "head: null tensor argument");
+  if (int rc = check_aligned({NamedPtr{src, "y / U"}, NP(W), NP(bias), NP(pooled), NP(logits),
+                              NP(lossv), NP(loss), NP(pred)},
+                             4))
+    return rc;
+  if (int rc = check_aligned({NP(labels)}, 8)) return rc;
+  return STGCN_OK;
+}
+// (after every argument check of either form)
+static int head_eval_fits(const stgcn_eval_desc_t *d) {
   if ((size_t)(d->C + d->classes + 8) * sizeof(float) > 64 * 1024)
     return fail(STGCN_E_UNSUPPORTED, "head: C + classes too large");
   return STGCN_OK;
@@ -584,6 +628,8 @@ int stgcn_head_eval(const stgcn_eval_desc_t *d, const float *y, const float *W, 
                     float *loss, int32_t *pred, void *metrics, void *stream) {
   int rc = head_eval_check(d, y, W, bias, labels, pooled, logits, lossv, loss, pred);
   if (rc) return rc;
+  if ((rc = check_aligned({NP(metrics)}, 8))) return rc;
+  if ((rc = head_eval_fits(d))) return rc;
   hipStream_t s = (hipStream_t)stream;
   const int64_t rows = (int64_t)d->N * d->C;
   hipLaunchKernelGGL(k_head_pool, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, y, pooled,
@@ -598,6 +644,9 @@ int stgcn_head_eval_u(const stgcn_eval_desc_t *d, const float *U, const float *s
   int rc = head_eval_check(d, U, W, bias, labels, pooled, logits, lossv, loss, pred);
   if (rc) return rc;
   if (!stats2 || !g2 || !b2) return fail(STGCN_E_INVALID, "head: null tensor argument");
+  if ((rc = check_aligned({NP(stats2), NP(g2), NP(b2)}, 4))) return rc;
+  if ((rc = check_aligned({NP(metrics)}, 8))) return rc;
+  if ((rc = head_eval_fits(d))) return rc;
   hipStream_t s = (hipStream_t)stream;
   const int64_t rows = (int64_t)d->N * d->C;
   hipLaunchKernelGGL(k_head_pool_u, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, U, stats2,
@@ -613,6 +662,11 @@ int stgcn_head_bwd(const stgcn_head_desc_t *d, const float *pooled, const float 
   if (!pooled || !logits || !W || !labels || !dloss || !dlogits || !dpooled || !dy || !dW ||
       !dbias)
     return fail(STGCN_E_INVALID, "head: null tensor argument");
+  if (int rc = check_aligned({NP(pooled), NP(logits), NP(W), NP(dloss), NP(dlogits), NP(dpooled),
+                              NP(dy), NP(dW), NP(dbias)},
+                             4))
+    return rc;
+  if (int rc = check_aligned({NP(labels)}, 8)) return rc;
   hipStream_t s = (hipStream_t)stream;
   const int64_t rows = (int64_t)d->N * d->C;
   hipLaunchKernelGGL(k_head_bwd_rows, dim3(d->N), dim3(256),
@@ -635,6 +689,11 @@ int stgcn_head_bwd_nc(const stgcn_head_desc_t *d, const float *pooled, const flo
   if (!pooled || !logits || !W || !labels || !dloss || !dlogits || !dpooled || !dy_nc || !dW ||
       !dbias)
     return fail(STGCN_E_INVALID, "head: null tensor argument");
+  if (int rc = check_aligned({NP(pooled), NP(logits), NP(W), NP(dloss), NP(dlogits), NP(dpooled),
+                              NP(dy_nc), NP(dW), NP(dbias)},
+                             4))
+    return rc;
+  if (int rc = check_aligned({NP(labels)}, 8)) return rc;
   hipStream_t s = (hipStream_t)stream;
   const int64_t rows = (int64_t)d->N * d->C;
   hipLaunchKernelGGL(k_head_bwd_rows, dim3(d->N), dim3(256),

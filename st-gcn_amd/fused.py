@@ -16,10 +16,26 @@ import torch
 from . import hip_lib
 
 
-def _f32c(t, name):
+def _aligned16(t):
+    """``t`` itself when its data starts on a 16-byte boundary, else a copy that
+    does (fresh storage; a contiguous ``t`` stays contiguous). For read-only
+    library inputs only."""
+    if t.data_ptr() % 16 == 0:
+        return t
+    return torch.empty_like(t).copy_(t.detach())
+
+
+def _f32c(t, name, inout=False):
+    """The tensor the library reads in place of ``t``: ``t`` checked, and -- the
+    block kernels read their inputs in 16-byte units (stgcn_hip.h, Conventions:
+    the library refuses a pointer off that boundary) -- an aligned copy of it
+    when it is a view that starts off one (a slice of a batch, a view into a flat
+    bucket). inout: never a copy -- the running statistics, updated in place, and
+    the inputs of calls that take them at 4-byte alignment (the fp32 SpatialConv
+    on its own)."""
     if t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda:
         raise RuntimeError(f"{name}: expected a contiguous float32 GPU tensor")
-    return t
+    return t if inout else _aligned16(t)
 
 
 def make_desc(x_shape, C_out, K, stride, pad, eps, momentum, training, need_dx=1, gamma=9,
@@ -204,11 +220,10 @@ def eval_forward(blocks, x, descs, links, preps):
         if cur is not None:
             cur = _f32c(cur.float().contiguous(), "x")
         sc, tc, bn1, bn2 = blk.spatialConv, blk.temporalConv, blk.batch_n, blk.batch_n_2
-        params = (sc.A, sc.W.weight, sc.W.bias, tc.weight, tc.bias, bn1.weight, bn1.bias,
-                  bn2.weight, bn2.bias, bn1.running_mean, bn1.running_var, bn2.running_mean,
-                  bn2.running_var)
-        for t in params:
-            _f32c(t, "block parameter")
+        params = tuple(_f32c(t, "block parameter") for t in (
+            sc.A, sc.W.weight, sc.W.bias, tc.weight, tc.bias, bn1.weight, bn1.bias,
+            bn2.weight, bn2.bias)) + tuple(_f32c(t, "running statistic", inout=True) for t in (
+                bn1.running_mean, bn1.running_var, bn2.running_mean, bn2.running_var))
         C_in, C_out = desc.C_in, desc.C_out
         shape = (desc.N, C_out, desc.T_out, desc.V)
         nel = shape[0] * shape[1] * shape[2] * shape[3]
@@ -228,7 +243,7 @@ def eval_forward(blocks, x, descs, links, preps):
             cur, *params, y, Z, U, stats, Wr, br, Za if blk.residual else None,
             None, None, None)], 0.0, 0, prep=hip_lib.ptr(prep))
         if cur is None:
-            pU, pstats, pg2, pb2 = prev
+            pU, pstats, pg2, pb2 = prev  # (pg2 / pb2: the previous block's aligned params)
             args.prev_U, args.prev_stats = hip_lib.ptr(pU), hip_lib.ptr(pstats)
             args.prev_g2, args.prev_b2 = hip_lib.ptr(pg2), hip_lib.ptr(pb2)
         hip_lib.check(lib.stgcn_block_fwd(ctypes.byref(desc), ctypes.byref(args), hip_lib.ptr(ws),
@@ -236,7 +251,7 @@ def eval_forward(blocks, x, descs, links, preps):
         if y is not None:
             cur, hold, prev = y, (iu if blk.residual else 1 - iu), None
         else:
-            cur, hold, prev = None, iu, (U, stats[2 * C_in:], bn2.weight, bn2.bias)
+            cur, hold, prev = None, iu, (U, stats[2 * C_in:], params[7], params[8])
     return ("y", cur) if cur is not None else ("u", prev)
 
 
@@ -258,7 +273,7 @@ class FoldPrep:
         training: the descriptors the buffers are formed for (an eval step keeps
         a FoldPrep of its own, so the two never share a buffer)."""
         lib = hip_lib.lib()
-        descs, weights, ptrs, out = [], [], [], []
+        descs, weights, ptrs, out, keep = [], [], [], [], []
         for i, (blk, desc) in enumerate(zip(blocks, stack_descs(blocks, x_shape, training))):
             sc, tc = blk.spatialConv, blk.temporalConv
             gemm = blk.gemm_mode()
@@ -275,8 +290,11 @@ class FoldPrep:
                     buf = torch.empty(nbytes, device=dev, dtype=torch.uint8)
                     self._bufs[i] = (key, buf)
                 descs.append(desc)
-                weights.append(hip_lib.FoldWeights(*[hip_lib.ptr(t) for t in (
-                    sc.A, sc.W.weight, sc.W.bias, tc.weight, tc.bias)]))
+                # (aligned copies stay alive in ``keep`` until the call is enqueued)
+                ws = [_f32c(t, "block parameter") for t in (
+                    sc.A, sc.W.weight, sc.W.bias, tc.weight, tc.bias)]
+                keep.append(ws)
+                weights.append(hip_lib.FoldWeights(*[hip_lib.ptr(t) for t in ws]))
                 ptrs.append(hip_lib.ptr(buf))
             out.append(buf)
         if descs:
@@ -315,8 +333,8 @@ def _chain_bwd_args(cc, dy, need_dx, C_in, dev, xref=None):
         prev_sums = torch.empty(2 * C_in, device=dev, dtype=torch.float64)
         dx_coef = (None if _observed(xref)
                    else torch.empty(5 * C_in, device=dev, dtype=torch.float32))
-        return (dy_sums, dy_coef, cc.prev_g2, cc.prev_b2, prev_sums, cc.prev_U, cc.prev_stats,
-                cc.x_stats, dx_coef)
+        return (dy_sums, dy_coef, _f32c(cc.prev_g2, "prev_g2"), _f32c(cc.prev_b2, "prev_b2"),
+                prev_sums, cc.prev_U, cc.prev_stats, cc.x_stats, dx_coef)
     return (dy_sums, dy_coef) + (None,) * 7
 
 
@@ -394,9 +412,9 @@ class StgcnBlockFn(torch.autograd.Function):
                  "rm1", "rv1", "rm2", "rv2")
         tensors = (x, A, W, bW, Wt, bWt, g1, b1, g2, b2, rm1, rv1, rm2, rv2)
         seed = _dropout_seed(drop, training)
-        for t, n in zip(tensors, names):
-            if not (xu and n == "x"):
-                _f32c(t, n)
+        x, A, W, bW, Wt, bWt, g1, b1, g2, b2, rm1, rv1, rm2, rv2 = (
+            t if xu and n == "x" else _f32c(t, n, inout=n[0] == "r")
+            for t, n in zip(tensors, names))
         N, C_in, T, V = x.shape
         K = A.shape[0]
         C_out = Wt.shape[0]
@@ -420,8 +438,9 @@ class StgcnBlockFn(torch.autograd.Function):
             None, None, None, G, cc and cc.x_stats, cc and cc.y_stats)], drop, seed,
             prep=hip_lib.ptr(prep))
         if xu:
+            pg2, pb2 = _f32c(cc.prev_g2, "prev_g2"), _f32c(cc.prev_b2, "prev_b2")
             args.prev_U, args.prev_stats = hip_lib.ptr(cc.prev_U), hip_lib.ptr(cc.prev_stats)
-            args.prev_g2, args.prev_b2 = hip_lib.ptr(cc.prev_g2), hip_lib.ptr(cc.prev_b2)
+            args.prev_g2, args.prev_b2 = hip_lib.ptr(pg2), hip_lib.ptr(pb2)
         ctx.x_lazy = xu
         hip_lib.check(lib.stgcn_block_fwd(ctypes.byref(desc), ctypes.byref(args),
                                           hip_lib.ptr(ws), nbytes, hip_lib.stream_handle(dev)))
@@ -446,7 +465,9 @@ class StgcnBlockFn(torch.autograd.Function):
         # from (N, C_out)) goes in as dy_nc; anything else as a contiguous dy
         dy_nc = _per_row(dy)
         dy_full = dy
-        dy = None if dy_nc is not None else dy.contiguous()
+        dy = None if dy_nc is not None else _aligned16(dy.contiguous())
+        if dy_nc is not None and dy_nc.data_ptr() % 16:  # (its (N, C) base, off a boundary)
+            dy_nc = _aligned16(dy_nc[:, :, 0, 0])
         desc = make_desc(x.shape, C_out, A.shape[0], stride, pad, eps, momentum, training,
                          need_dx=need_dx, **_gemm_flags(ctx.gemm))
         dy_sums, dy_coef, pg2, pb2, psums, pU, pst, xst, dx_coef = _chain_bwd_args(
@@ -469,7 +490,7 @@ class StgcnBlockFn(torch.autograd.Function):
         rc = lib.stgcn_block_bwd(ctypes.byref(desc), ctypes.byref(args), hip_lib.ptr(ws), nbytes,
                                  hip_lib.stream_handle(x.device))
         if rc == hip_lib.E_UNSUPPORTED and dy_nc is not None:  # (needs the full dy)
-            dy = dy_full.contiguous()
+            dy = _aligned16(dy_full.contiguous())
             args.dy, args.dy_nc = hip_lib.ptr(dy), None
             rc = lib.stgcn_block_bwd(ctypes.byref(desc), ctypes.byref(args), hip_lib.ptr(ws),
                                      nbytes, hip_lib.stream_handle(x.device))
@@ -499,11 +520,11 @@ class StgcnResBlockFn(torch.autograd.Function):
         seed = _dropout_seed(drop, training)
         names = ("x", "A", "W", "bW", "Wt", "bWt", "g1", "b1", "g2", "b2",
                  "rm1", "rv1", "rm2", "rv2")
-        for t, n in zip((x, A, W, bW, Wt, bWt, g1, b1, g2, b2, rm1, rv1, rm2, rv2), names):
-            _f32c(t, n)
+        x, A, W, bW, Wt, bWt, g1, b1, g2, b2, rm1, rv1, rm2, rv2 = (
+            _f32c(t, n, inout=n[0] == "r")
+            for t, n in zip((x, A, W, bW, Wt, bWt, g1, b1, g2, b2, rm1, rv1, rm2, rv2), names))
         if Wr is not None:
-            _f32c(Wr, "Wr")
-            _f32c(br, "br")
+            Wr, br = _f32c(Wr, "Wr"), _f32c(br, "br")
         N, C_in, T, V = x.shape
         K = A.shape[0]
         C_out = Wt.shape[0]
@@ -538,7 +559,7 @@ class StgcnResBlockFn(torch.autograd.Function):
         x, Z, Za, y, stats, A, W, bW, Wt, g1, b1, g2, b2, Wr, G = ctx.saved_tensors
         stride, pad, eps, momentum, training = ctx.cfg
         need_dx = bool(ctx.needs_input_grad[0])
-        dy = dy.contiguous()
+        dy = _aligned16(dy.contiguous())
         C_out = Wt.shape[0]
         desc = make_desc(x.shape, C_out, A.shape[0], stride, pad, eps, momentum, training,
                          need_dx=need_dx, residual=True,
@@ -576,8 +597,10 @@ class SpatialConvFn(torch.autograd.Function):
     def forward(ctx, x, A, W, bW, bf16=False):
         lib = hip_lib.lib()
         x = x.contiguous()
-        for t, n in ((x, "x"), (A, "A"), (W, "W"), (bW, "bW")):
-            _f32c(t, n)
+        # (the fp32 kernels read these at 4-byte alignment: a misaligned x takes the
+        # narrower gather; the bf16 kernels get aligned copies)
+        x, A, W, bW = (_f32c(t, n, inout=not bf16)
+                       for t, n in ((x, "x"), (A, "A"), (W, "W"), (bW, "bW")))
         N, C_in, T, V = x.shape
         K = A.shape[0]
         C_out = W.shape[0] // K
@@ -599,6 +622,8 @@ class SpatialConvFn(torch.autograd.Function):
         x, A, W, bW = ctx.saved_tensors
         dout = dout.contiguous()
         desc = ctx.desc
+        if desc.flags & hip_lib.F_BF16:
+            dout = _aligned16(dout)
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         dA, dW, dbW = (torch.empty_like(t) for t in (A, W, bW))
         nbytes = lib.stgcn_spatial_workspace_bytes(ctypes.byref(desc), 1)

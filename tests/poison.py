@@ -28,7 +28,7 @@ import sys
 import torch
 
 GUARD = 64 * 1024   # bytes of fill before and after every buffer
-ALIGN = 256         # buffers start at this alignment (prev_U needs 16)
+ALIGN = 256         # buffers start at this alignment (the library asks for 16), plus ``skew``
 MODULES = ("fused", "network", "train_ops", "model")
 FILLS = (0x00, 0xFF, 0x4B)
 
@@ -70,12 +70,17 @@ def _call_site():
     return (os.path.basename(f.f_code.co_filename), f.f_lineno, f.f_code.co_name)
 
 
-def _alloc(shape, dtype, device, fill, kind, name=None):
+def _alloc(shape, dtype, device, fill, kind, name=None, skew=0):
+    """skew: bytes the buffer starts past its ALIGN boundary (a multiple of the
+    element size below ALIGN), as a view into a flat bucket or a slice of a batch
+    does; both guard bands keep at least GUARD bytes."""
     shape = tuple(int(s) for s in shape)
     item = torch.empty((), dtype=dtype).element_size()
+    assert 0 <= skew < ALIGN and skew % item == 0, (skew, item)
     nbytes = math.prod(shape) * item
-    backing = torch.full((nbytes + 2 * GUARD + ALIGN,), fill, dtype=torch.uint8, device=device)
-    offset = GUARD + (-(backing.data_ptr() + GUARD)) % ALIGN
+    backing = torch.full((nbytes + 2 * GUARD + 2 * ALIGN,), fill, dtype=torch.uint8,
+                         device=device)
+    offset = GUARD + (-(backing.data_ptr() + GUARD)) % ALIGN + skew
     strides, acc = [], 1
     for s in reversed(shape):
         strides.append(acc)
@@ -86,7 +91,7 @@ def _alloc(shape, dtype, device, fill, kind, name=None):
         backing.untyped_storage(), (backing.storage_offset() + offset) // item, shape,
         tuple(reversed(strides)))
     assert nbytes == 0 or (t.data_ptr() == backing.data_ptr() + offset
-                           and t.data_ptr() % ALIGN == 0)
+                           and t.data_ptr() % ALIGN == skew)
     a = Allocation(len(_RECORD), kind, name, backing, offset, t, fill, _call_site())
     _RECORD.append(a)
     return a
@@ -160,12 +165,13 @@ def poisoned(pkg, fill, device_type="cuda"):
             m.torch = torch
 
 
-def guarded(t, fill, device="cuda:0", name=None, readonly=True):
+def guarded(t, fill, device="cuda:0", name=None, readonly=True, skew=0):
     """A copy of the test input ``t`` on ``device`` inside a guarded backing
     filled with ``fill`` (same dtype and shape, contiguous). readonly: its bytes
-    are remembered and ``check_inputs()`` requires them unchanged."""
+    are remembered and ``check_inputs()`` requires them unchanged. skew: the
+    copy starts that many bytes past a 256-byte boundary (``_alloc``)."""
     src = t.detach().contiguous()
-    a = _alloc(src.shape, src.dtype, device, fill, "input", name)
+    a = _alloc(src.shape, src.dtype, device, fill, "input", name, skew=skew)
     a.tensor.copy_(src)
     if readonly:
         a.snapshot = a.view_bytes().cpu().clone()

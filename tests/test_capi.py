@@ -238,3 +238,187 @@ def test_head_link_decision(pkg):
     assert not pkg.fused.head_link_ok(m.conv[-1])
     h.remove()
     assert pkg.fused.head_link_ok(m.conv[-1])
+
+
+# ---------------------------------------------------------------------------
+# The alignment contract (include/stgcn_hip.h, Conventions): with fake pointer
+# values, no GPU touched -- every call below stops at an argument check.
+# ---------------------------------------------------------------------------
+_FWD_PTRS = ("x", "A", "W", "bW", "Wt", "bWt", "g1", "b1", "g2", "b2", "rm1", "rv1", "rm2",
+             "rv2", "y", "Z", "U", "stats", "Wr", "br", "Za", "G", "x_stats", "y_stats", "prep",
+             "prev_U", "prev_stats", "prev_g2", "prev_b2")
+_BWD_PTRS = ("dy", "x", "Z", "U", "stats", "A", "W", "bW", "Wt", "g1", "b1", "g2", "b2", "dx",
+             "dA", "dW", "dbW", "dWt", "dbWt", "dg1", "db1", "dg2", "db2", "Wr", "Za", "y", "dWr",
+             "dbr", "G", "dy_sums", "prev_g2", "prev_b2", "prev_sums", "prev_U", "prev_stats",
+             "x_stats", "dx_coef", "dy_coef", "prep", "dy_nc")
+_NATURAL = ("rm1", "rv1", "rm2", "rv2", "prev_stats")      # fp32, taken at 4 bytes
+_FP64 = ("x_stats", "y_stats", "dy_sums", "prev_sums")     # fp64 blocks: 16 all the same
+_OK = 256
+
+
+def _named(lib, name, align):
+    return f"{name}: must be {align}-byte aligned".encode() in lib.stgcn_last_error()
+
+
+def _block_call(pkg, lib, which, ws=None, **ptrs):
+    """stgcn_block_fwd / _bwd of a folded f16x2 block (every optional argument
+    applies to it) with every pointer argument a 256-aligned fake but ``ptrs``;
+    no workspace bytes, so a call that passes the argument checks stops at
+    "workspace too small"."""
+    hl = pkg.hip_lib
+    d = _desc(pkg, flags=12)
+    a = hl.FwdArgs() if which == "fwd" else hl.BwdArgs()
+    for n in (_FWD_PTRS if which == "fwd" else _BWD_PTRS):
+        setattr(a, n, ptrs.get(n, _OK))
+    if which == "bwd":
+        a.dx_deferred = _OK     # (a host int: no alignment asked)
+    fn = lib.stgcn_block_fwd if which == "fwd" else lib.stgcn_block_bwd
+    return fn(ctypes.byref(d), ctypes.byref(a), ws, 0, None)
+
+
+@pytest.mark.parametrize("which", ["fwd", "bwd"])
+def test_block_pointer_alignment_is_checked_by_name(pkg, lib, which):
+    assert _block_call(pkg, lib, which) == -1
+    assert b"workspace too small" in lib.stgcn_last_error()
+    assert _block_call(pkg, lib, which, ws=_OK) == -1
+    assert b"workspace too small" in lib.stgcn_last_error()
+    for off in (4, 8, 12):
+        assert _block_call(pkg, lib, which, ws=_OK + off) == -1
+        assert _named(lib, "workspace", 16), lib.stgcn_last_error()
+    for name in (_FWD_PTRS if which == "fwd" else _BWD_PTRS):
+        if name in _NATURAL:
+            for off in (4, 8, 12):   # natural alignment: accepted
+                assert _block_call(pkg, lib, which, **{name: _OK + off}) == -1
+                assert b"workspace too small" in lib.stgcn_last_error(), (name, off)
+            assert _block_call(pkg, lib, which, **{name: _OK + 2}) == -1
+            assert _named(lib, name, 4), (name, lib.stgcn_last_error())
+            continue
+        for off in (4, 8) if name in _FP64 else (4,):
+            assert _block_call(pkg, lib, which, **{name: _OK + off}) == -1
+            if name == "prev_U" and which == "fwd":   # (its own, older message)
+                assert b"16-byte aligned prev_U" in lib.stgcn_last_error()
+            else:
+                assert _named(lib, name, 16), (name, off, lib.stgcn_last_error())
+
+
+def test_ignored_block_pointers_are_not_checked(pkg, lib):
+    """dx without need_dx and U of a residual block are ignored, misaligned or not."""
+    hl = pkg.hip_lib
+    d = _desc(pkg, need_dx=0)
+    b = hl.BwdArgs(*([_OK] * 23))
+    b.dx = _OK + 4
+    assert lib.stgcn_block_bwd(ctypes.byref(d), ctypes.byref(b), None, 0, None) == -1
+    assert b"workspace too small" in lib.stgcn_last_error()
+    d = _desc(pkg, flags=1)
+    a = hl.FwdArgs(*([_OK] * 21))
+    a.U = _OK + 4
+    assert lib.stgcn_block_fwd(ctypes.byref(d), ctypes.byref(a), None, 0, None) == -1
+    assert b"workspace too small" in lib.stgcn_last_error()
+
+
+def test_spatial_pointer_alignment_is_checked_by_name(pkg, lib):
+    """SpatialConv on its own: outputs and the workspace at 16 bytes; the inputs at
+    16 under STGCN_F_BF16, at their natural 4 on the fp32 path (which routes a
+    misaligned x / dout to its narrower kernels)."""
+    fwd, bwd = ("x", "A", "W", "bW", "out"), ("dout", "x", "A", "W", "bW", "dx", "dA", "dW", "dbW")
+    inputs = ("x", "A", "W", "bW", "dout")
+    for flags in (0, 2):
+        d = pkg.hip_lib.SpatialDesc(N=8, C_in=64, C_out=64, T=30, V=25, K=3, flags=flags)
+        for names, fn in ((fwd, lib.stgcn_spatial_fwd), (bwd, lib.stgcn_spatial_bwd)):
+            assert fn(ctypes.byref(d), *([_OK] * len(names)), None, 0, None) == -1
+            assert b"workspace too small" in lib.stgcn_last_error()
+            assert fn(ctypes.byref(d), *([_OK] * len(names)), _OK + 4, 0, None) == -1
+            assert _named(lib, "workspace", 16), lib.stgcn_last_error()
+            for i, name in enumerate(names):
+                vals = [_OK] * len(names)
+                vals[i] = _OK + 4
+                assert fn(ctypes.byref(d), *vals, None, 0, None) == -1
+                if name in inputs and flags == 0:
+                    assert b"workspace too small" in lib.stgcn_last_error(), name
+                    vals[i] = _OK + 2
+                    assert fn(ctypes.byref(d), *vals, None, 0, None) == -1
+                    assert _named(lib, name, 4), (name, lib.stgcn_last_error())
+                else:
+                    assert _named(lib, name, 16), (name, flags, lib.stgcn_last_error())
+
+
+def test_fold_prep_pointer_alignment_is_checked_by_name(pkg, lib):
+    hl = pkg.hip_lib
+    d = _desc(pkg, flags=12)
+    names = ("A", "W", "bW", "Wt", "bWt")
+    for bad in names + ("prep",):
+        w = hl.FoldWeights(*[(_OK + 4 if n == bad else _OK) for n in names])
+        prep = (ctypes.c_void_p * 1)(_OK + 4 if bad == "prep" else _OK)
+        assert lib.stgcn_fold_prep(1, ctypes.byref(d), ctypes.byref(w), prep, None) == -1
+        assert _named(lib, bad, 16), (bad, lib.stgcn_last_error())
+
+
+def test_head_and_adam_take_natural_alignment(pkg, lib):
+    """The head and Adam kernels access one element at a time: fp32 tensors are
+    taken at 4 bytes (a view into a flat gradient bucket), int64 labels, the
+    metrics block and the Adam table at 8. A head that is too large for its LDS
+    is refused (-2) after the alignment checks: that is how an accepted fake
+    call ends here without a launch."""
+    hl = pkg.hip_lib
+    big = hl.HeadDesc(4, 64, 54, 20000)
+    ebig = hl.EvalDesc(4, 64, 54, 20000, 1)
+    calls = [  # (function, descriptor, argument names)
+        (lib.stgcn_head_fwd, big, ("y", "W", "bias", "labels", "pooled", "logits", "lossv",
+                                   "loss")),
+        (lib.stgcn_head_fwd_u, big, ("U", "stats2", "g2", "b2", "W", "bias", "labels", "pooled",
+                                     "logits", "lossv", "loss")),
+        (lib.stgcn_head_eval, ebig, ("y / U", "W", "bias", "labels", "pooled", "logits", "lossv",
+                                     "loss", "pred", "metrics")),
+        (lib.stgcn_head_eval_u, ebig, ("y / U", "stats2", "g2", "b2", "W", "bias", "labels",
+                                       "pooled", "logits", "lossv", "loss", "pred", "metrics")),
+    ]
+    for fn, d, names in calls:
+        for i, name in enumerate(names):
+            wide = name in ("labels", "metrics")
+            vals = [_OK + (8 if n in ("labels", "metrics") else 4) for n in names]
+            if name == "metrics":
+                # (checked after the LDS limit's -2 would hit: take a head that fits,
+                # and let the call stop at the misaligned block itself)
+                d2 = hl.EvalDesc(4, 64, 54, 10, 1)
+                vals[i] = _OK + 4
+                assert fn(ctypes.byref(d2), *vals, None) == -1
+                assert _named(lib, name, 8), (name, lib.stgcn_last_error())
+                continue
+            assert fn(ctypes.byref(d), *vals, None) == -2, (name, lib.stgcn_last_error())
+            assert b"too large" in lib.stgcn_last_error()
+            vals[i] = _OK + (4 if wide else 2)
+            assert fn(ctypes.byref(d), *vals, None) == -1
+            assert _named(lib, name, 8 if wide else 4), (name, lib.stgcn_last_error())
+    small = hl.HeadDesc(4, 64, 54, 10)
+    for fn, names in ((lib.stgcn_head_bwd, ("pooled", "logits", "W", "labels", "dloss", "dlogits",
+                                            "dpooled", "dy", "dW", "dbias")),
+                      (lib.stgcn_head_bwd_nc, ("pooled", "logits", "W", "labels", "dloss",
+                                               "dlogits", "dpooled", "dy_nc", "dW", "dbias"))):
+        for i, name in enumerate(names):
+            vals = [_OK] * len(names)
+            vals[i] = _OK + (4 if name == "labels" else 2)
+            assert fn(ctypes.byref(small), *vals, None) == -1
+            assert _named(lib, name, 8 if name == "labels" else 4), (name, lib.stgcn_last_error())
+    assert lib.stgcn_eval_metrics_reset(_OK + 4, 10, None) == -1
+    assert _named(lib, "metrics", 8)
+    # Adam: the table at 8 bytes, its tensors at 4 (views into a flat bucket pass)
+    f64 = [ctypes.c_double(v) for v in (1e-3, 0.9, 0.999, 1e-8, 0.0)]
+    assert lib.stgcn_adam_step(_OK + 4, 1, 1, *f64, 1, None) == -1
+    assert _named(lib, "dev_table", 8)
+    assert lib.stgcn_adam_step_dev(_OK + 4, 1, 1, *f64, _OK, None) == -1
+    assert _named(lib, "dev_table", 8)
+    assert lib.stgcn_adam_step_dev(_OK, 1, 1, *f64, _OK + 2, None) == -1
+    assert _named(lib, "step", 4)
+    nbytes = lib.stgcn_adam_table_bytes(2)
+    host = (ctypes.c_char * nbytes)()
+    chunks = ctypes.c_int64(0)
+    ok = (hl.AdamTensor * 2)(hl.AdamTensor(_OK + 12, _OK + 4, _OK + 8, _OK, 1875),
+                             hl.AdamTensor(_OK + 4, _OK + 12, _OK + 4, _OK + 8, 5000))
+    assert lib.stgcn_adam_build_table(ok, 2, host, nbytes, ctypes.byref(chunks)) == 0
+    assert chunks.value == 1 + 3
+    for field in ("param", "grad", "exp_avg", "exp_avg_sq"):
+        t = hl.AdamTensor(_OK, _OK, _OK, _OK, 64)
+        setattr(t, field, _OK + 2)
+        bad = (hl.AdamTensor * 2)(ok[0], t)
+        assert lib.stgcn_adam_build_table(bad, 2, host, nbytes, ctypes.byref(chunks)) == -1
+        assert b"tensor 1" in lib.stgcn_last_error() and b"4-byte aligned" in lib.stgcn_last_error()

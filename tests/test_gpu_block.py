@@ -45,9 +45,12 @@ def _fold_prep(pkg, cu, xshape, C_out, K, stride, gemm, empty=torch.empty):
     nbytes = lib.stgcn_fold_prep_bytes(ctypes.byref(d))
     assert nbytes > 0, "the block does not fold"
     buf = empty(nbytes, device=DEV, dtype=torch.uint8)
-    w = hl.FoldWeights(*[hl.ptr(cu[k]) for k in (
+    # (stgcn_fold_prep takes 16-byte aligned weights, stgcn_hip.h Conventions: the
+    # package's own aligned copy of a weight placed off a boundary, as FoldPrep.run)
+    ws = [pkg.fused._f32c(cu[k].detach(), k) for k in (
         "spatialConv.A", "spatialConv.W.weight", "spatialConv.W.bias", "temporalConv.weight",
-        "temporalConv.bias")])
+        "temporalConv.bias")]
+    w = hl.FoldWeights(*[hl.ptr(t) for t in ws])
     hl.check(lib.stgcn_fold_prep(1, (hl.Desc * 1)(d), (hl.FoldWeights * 1)(w),
                                  (ctypes.c_void_p * 1)(hl.ptr(buf)), hl.stream_handle(DEV)))
     return buf

@@ -167,3 +167,43 @@ def test_proxy_is_gone_after_the_context(pkg):
     # the record outlives the context (read after the run), and a new context starts afresh
     with poison.poisoned(pkg, 0x00, device_type="cpu"):
         assert poison.allocations() == []
+
+
+@pytest.mark.parametrize("skew", [0, 4, 8, 12])
+def test_skewed_inputs_keep_their_guards(cpu_poison, skew):
+    """guarded(..., skew=): the tensor starts ``skew`` bytes past a 256-byte
+    boundary (what a view into a flat bucket or x[1:] of an odd-sized batch
+    gives), is contiguous, survives the runners' ``.float().contiguous()``
+    without a copy, and a write one element before its start or past its end
+    still trips the guard check."""
+    pkg, proxy, fill = cpu_poison
+    src = torch.arange(30, dtype=torch.float32).reshape(2, 3, 5)
+    g = poison.guarded(src, fill, device="cpu", name="x", skew=skew)
+    assert g.data_ptr() % 16 == skew and g.data_ptr() % poison.ALIGN == skew
+    assert g.is_contiguous() and torch.equal(g, src)
+    same = g.float().contiguous()
+    assert same.data_ptr() == g.data_ptr()
+    assert same.untyped_storage().data_ptr() == g.untyped_storage().data_ptr()
+    a = poison.allocations()[-1]
+    assert a.tensor is g and a.offset % 16 == (skew - a.backing.data_ptr()) % 16
+    pre, post = a.guards()
+    assert pre.numel() >= poison.GUARD and post.numel() >= poison.GUARD
+    assert torch.equal(a.view_bytes().view(torch.float32), src.reshape(-1))
+    poison.check_guards()
+    poison.check_inputs()
+    for pos in (a.offset - 4, a.offset - 1, a.offset + a.nbytes, a.offset + a.nbytes + 3):
+        a.backing[pos] = fill ^ 0x01
+        with pytest.raises(AssertionError, match="guard band overrun"):
+            poison.check_guards()
+        a.backing[pos] = fill
+        poison.check_guards()
+    if skew % 8 == 0:   # int64 labels: multiples of 8 only
+        lab = poison.guarded(torch.tensor([3, 1, 4]), fill, device="cpu", name="labels",
+                             skew=skew)
+        assert lab.dtype == torch.int64 and lab.data_ptr() % 16 == skew
+        assert lab.contiguous().data_ptr() == lab.data_ptr()
+    else:
+        with pytest.raises(AssertionError):
+            poison.guarded(torch.tensor([3, 1, 4]), fill, device="cpu", skew=skew)
+    with pytest.raises(AssertionError):
+        poison.guarded(src, fill, device="cpu", skew=skew + 2)
