@@ -1546,11 +1546,22 @@ namespace stgcn {
 // padded to Vp = round4(V) (P's pad positions are 0). k-step = 16 positions:
 // lane half h takes 4-groups 2s, 2s+1 of frame half h: A = one ds_read_b128 per
 // plane, B per tap = two ds_read_b64 per plane (row pitches 8 mod 16 / 4 mod 8
-// elements: conflict-free). Images: 3 planes each of P [64][KP] and Q
-// [32][QF*Vp], double-buffered at stride 1 (157.5 KiB at V = 18; one buffer and
-// a second barrier at stride 2); the next item is loaded
-// into registers (4-joint groups, fp32 dwords) under this item's MFMAs, split
-// and written after them; one barrier per item.
+// elements: conflict-free). LDS: NPL planes of P [ROWS][KP], double-buffered,
+// and ONE Q image per plane, [32][NS frame slots * Vp], kept as a ring across
+// the split's items: item i + 1's window is item i's moved on by NEWF = SIN * FT
+// frames, so OLDF = QF - NEWF of its QF frames are already there as split
+// planes and only the NEWF incoming ones are staged. An item at ring phase ph
+// (0 at the split's first item, + NEWF mod NS per item) has window frame f in
+// slot (ph + f) mod NS; the next item's new frames go to the slots
+// (ph + QF .. ph + QF + NEWF - 1) mod NS, which this item does not read
+// (QF + NEWF <= NS), so the next item is loaded into registers (4-joint groups,
+// fp32 dwords) under this item's MFMAs, split and written in their shadow, and
+// one barrier per item still orders everything. At the split's first item and
+// at every clip start inside its run the OLDF frames the ring cannot supply are
+// loaded, written and fenced by a second barrier before the item's MFMAs (once
+// per clip: 75 / 38 / 19 items at T = 300 / 150 / 75). The B reads take their
+// slot from SIN + NT lane bases formed once per item (phase, tap group and lane
+// half folded in, wrap included), so no read gains address arithmetic.
 // ---------------------------------------------------------------------------
 template <int V, int SIN, int NPL = 3, int MR = 1>
 struct WgX3Geo {
@@ -1562,28 +1573,73 @@ struct WgX3Geo {
   static constexpr int KSTEPS = KP / 16;
   static constexpr int HF = FT / 2;
   static constexpr int PPITCH = KP + 8;
-  static constexpr int QF = SIN * (FT - 1) + 9;
-  static constexpr int QP0 = QF * Vp;
+  static constexpr int QF = SIN * (FT - 1) + 9;  // frames of an item's Q window
+  static constexpr int NEWF = SIN * FT;          // frames the window moves on per item
+  static constexpr int OLDF = QF - NEWF;         // frames shared with the previous item's window
+  static constexpr int NS = (QF + NEWF + 7) & ~7;  // ring slots: 16 (stride 1), 24 (stride 2)
+  static constexpr int QP0 = NS * Vp;
   static constexpr int QPITCH = QP0 % 8 == 0 ? QP0 + 4 : QP0;
   static constexpr int CB = 32;
   static constexpr int PPL = ROWS * PPITCH * 2;  // bytes per P plane
   static constexpr int QPL = CB * QPITCH * 2;  // bytes per Q plane
-  static constexpr int BUF = NPL * (PPL + QPL);
-  // double-buffered where it fits (stride 1; NPL = 2: stride 2 too); else one
-  // buffer written between two barriers (stride 2, three planes: 15 Q frames)
-  static constexpr int NBUF = 2 * BUF <= 160 * 1024 ? 2 : 1;
-  static constexpr int LDS = NBUF * BUF;
+  static constexpr int PBUF = NPL * PPL;       // one P buffer
+  // two P buffers, then the Q ring (every instance double-buffers P: 128.5 KiB /
+  // 148.5 KiB at NPL = 2, MR = 2, stride 1 / 2; 156.75 KiB at NPL = 3, stride 2)
+  static constexpr int LDS = 2 * PBUF + NPL * QPL;
   // (the epilogue's slab tile [ROWS][CB][9] reuses the staging LDS; the launch
   // allocates at least that much -- one workgroup per CU either way)
   static constexpr int TILE = ROWS * CB * 9 * 4;
   static constexpr int LDSK = LDS > TILE ? LDS : TILE;
-  static constexpr int PG = FT * G4;  // 4-joint groups per P row
-  static constexpr int QG = QF * G4;  // ... per Q row
+  static constexpr int PG = FT * G4;    // 4-joint groups per P row
+  static constexpr int QG = NEWF * G4;  // ... per Q row, an item's new frames
+  static constexpr int OG = OLDF * G4;  // ... per Q row, a refill's old frames
   static constexpr int NGRP = ROWS * PG + CB * QG;
   static constexpr int GPT = (NGRP + 511) / 512;
+  static constexpr int OGPT = (CB * OG + 511) / 512;
+  // the ring: slot of window frame f of an item at phase ph, and the next item's phase
+  static constexpr int slot(int ph, int f) { return ph + f >= NS ? ph + f - NS : ph + f; }
+  static constexpr int next_phase(int ph) { return slot(ph, NEWF); }
+  // B fragments: lane base index of (frame fr of the lane half, tap t of the
+  // wave's group) and the window frame that base ci holds for tap group q0 and
+  // lane half hi
+  static constexpr int bidx(int fr, int t) { return SIN * fr + t; }
+  static constexpr int bframe(int ci, int q0, int hi) { return ci + q0 + hi * SIN * HF; }
+  static constexpr bool ring_ok() {
+    for (int ph = 0; ph < NS; ph += NEWF) {
+      const int phn = next_phase(ph);
+      if (phn % NEWF != 0 || phn >= NS) return false;
+      for (int f = 0; f < QF; ++f) {
+        // distinct frames of a window in distinct slots
+        for (int f2 = 0; f2 < f; ++f2)
+          if (slot(ph, f) == slot(ph, f2)) return false;
+        // a frame keeps its slot for as long as it stays in the window
+        if (f >= NEWF && slot(ph, f) != slot(phn, f - NEWF)) return false;
+        // the slots staged for the next item (its frames OLDF..QF-1, written
+        // under this item's MFMAs) are none of those this item reads
+        for (int j = 0; j < NEWF; ++j)
+          if (slot(phn, OLDF + j) == slot(ph, f)) return false;
+      }
+      // every B read (tap group q0 of NT taps, tap t, staging group g of the 2 *
+      // KSTEPS a lane half walks, lane half hi) addresses the slot of the window
+      // frame SIN * m + q that P's frame m = hi * HF + g / G4 meets at tap q
+      for (int tq = 0; tq < 4; ++tq) {
+        const int q0 = tq ? 1 + 2 * tq : 0, nt = tq ? 2 : 3;
+        for (int t = 0; t < nt; ++t)
+          for (int g = 0; g < 2 * KSTEPS; ++g)
+            for (int hi = 0; hi < 2; ++hi) {
+              const int ci = bidx(g / G4, t), f = bframe(ci, q0, hi);
+              if (ci >= SIN + nt || f >= QF) return false;
+              if (f != SIN * (hi * HF + g / G4) + q0 + t) return false;
+            }
+      }
+    }
+    return true;
+  }
   static_assert(KP % 16 == 0 && PPITCH % 16 == 8 && QPITCH % 8 == 4, "conflict-free pitches");
   static_assert(PPL % 16 == 0 && QPL % 16 == 0, "plane alignment");
   static_assert(LDS <= 160 * 1024, "LDS budget");
+  static_assert(QF + NEWF <= NS && NS % NEWF == 0 && 2 * KSTEPS == HF * G4, "ring geometry");
+  static_assert(ring_ok(), "ring slots: reads meet the staged frames, writes miss the live ones");
 };
 
 // NPL = 2: fp32 as 2-way fp16 splits of the power-of-two-scaled operands (P and
@@ -1645,8 +1701,15 @@ __global__ __launch_bounds__(512, 1) void k_wgrad_x3(WgradParams p) {
   const int it0 = split * per, it1 = min(total, it0 + per);
   const int MV = p.M * V, TV = p.T_src * V;
 
-  // staging groups of this thread: P (row, frame, joint group) or Q (channel, ...)
-  int grow[G::GPT], gfr[G::GPT], gv0[G::GPT], gl[G::GPT];
+  char *const qring = lds + 2 * G::PBUF;
+  // staging groups of this thread: P (row, frame, joint group) or Q (channel,
+  // new frame of the window, joint group)
+  // per group (three registers: this kernel has none to spare): gfv = frame |
+  // first joint << 8 | row << 16; gl = LDS byte offset within a plane (-1: no
+  // group; Q: without the frame slot, which moves with the ring phase); gsrc =
+  // source element offset within the clip at m0 = 0 resp. window start 0 (-1:
+  // no group, or a row / channel past the tensor's)
+  int gfv[G::GPT], gl[G::GPT], gsrc[G::GPT];
   bool isq[G::GPT];
 #pragma unroll
   for (int k = 0; k < G::GPT; ++k) {
@@ -1655,33 +1718,39 @@ __global__ __launch_bounds__(512, 1) void k_wgrad_x3(WgradParams p) {
     if (isq[k]) e -= G::ROWS * G::PG;
     const int per_row = isq[k] ? G::QG : G::PG;
     const int row = e / per_row, g = e - row * per_row;
-    grow[k] = row;
-    gfr[k] = g / G::G4;
-    gv0[k] = (g % G::G4) * 4;
-    const bool live = isq[k] ? row < G::CB : true;
-    // LDS byte offset within a plane (-1: no group)
-    gl[k] = (!live || (isq[k] && e >= G::CB * G::QG)) ? -1
-            : isq[k] ? (row * G::QPITCH + gfr[k] * G::Vp + gv0[k]) * 2
-                     : (row * G::PPITCH + gfr[k] * G::Vp + gv0[k]) * 2;
+    const int fr = g / G::G4, v0 = (g % G::G4) * 4;
+    gfv[k] = fr | v0 << 8 | row << 16;
+    const bool dead = isq[k] && e >= G::CB * G::QG;
+    gl[k] = dead ? -1
+            : isq[k] ? (row * G::QPITCH + v0) * 2
+                     : (row * G::PPITCH + fr * G::Vp + v0) * 2;
+    const bool in = !dead && (isq[k] ? c0 + row < p.C : r0 + row < p.R);
+    gsrc[k] = !in ? -1
+              : isq[k] ? (c0 + row) * TV + (G::OLDF + fr) * V + v0
+                       : (r0 + row) * MV + fr * V + v0;
   }
+  auto gfr = [&](int k) __attribute__((always_inline)) { return gfv[k] & 255; };
+  auto gv0 = [&](int k) __attribute__((always_inline)) { return (gfv[k] >> 8) & 255; };
+  auto grow = [&](int k) __attribute__((always_inline)) { return gfv[k] >> 16; };
   float st[G::GPT][4];
   unsigned qval = 0;  // QBN: bit 2k + j = pair j of staging group k lies inside the clip
+  // P's FT frames and the NEWF frames that item's Q window adds to the previous one's
   auto load_item = [&](int item) __attribute__((always_inline)) {
     if constexpr (QBN) qval = 0;
     const int n = item / p.n_mtiles, m0 = (item - n * p.n_mtiles) * G::FT;
     const __amdgpu_buffer_rsrc_t rp = make_rsrc(p.P + (int64_t)n * p.p_bstride, p.p_bstride);
     const __amdgpu_buffer_rsrc_t rq = make_rsrc(p.Q + (int64_t)n * p.q_bstride, p.q_bstride);
+    const int tw = SIN * m0 + p.off;  // the window's first source frame
 #pragma unroll
     for (int k = 0; k < G::GPT; ++k) {
       unsigned base;
       if (isq[k]) {
-        const int c = c0 + grow[k], t = SIN * m0 + p.off + gfr[k];
-        const bool ok = gl[k] >= 0 && c < p.C && t >= 0 && t < p.T_src;
-        base = ok ? (unsigned)(c * TV + t * V + gv0[k]) * 4u : kOOB;
+        const int t = tw + G::OLDF + gfr(k);
+        const bool ok = gsrc[k] >= 0 && t >= 0 && t < p.T_src;
+        base = ok ? (unsigned)(gsrc[k] + tw * V) * 4u : kOOB;
       } else {
-        const int r = r0 + grow[k], m = m0 + gfr[k];
-        const bool ok = gl[k] >= 0 && r < p.R && m < p.M;
-        base = ok ? (unsigned)(r * MV + m * V + gv0[k]) * 4u : kOOB;
+        const bool ok = gsrc[k] >= 0 && m0 + gfr(k) < p.M;
+        base = ok ? (unsigned)(gsrc[k] + m0 * V) * 4u : kOOB;
       }
       // P / Q split of the staging groups falls on wave boundaries (64 * PG is a
       // multiple of 64): a wave-uniform descriptor choice (no waterfall loop)
@@ -1691,9 +1760,9 @@ __global__ __launch_bounds__(512, 1) void k_wgrad_x3(WgradParams p) {
       // frame; pad pairs read 0 through an OOB offset)
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
-        const unsigned off = gv0[k] + 2 * j < V ? base + 8u * j : kOOB;
+        const unsigned off = gv0(k) + 2 * j < V ? base + 8u * j : kOOB;
         if constexpr (QBN)  // (P's groups: always live; their zeros pass the identity)
-          qval |= (!q_k || (base != kOOB && gv0[k] + 2 * j < V)) ? 1u << (2 * k + j) : 0u;
+          qval |= (!q_k || (base != kOOB && gv0(k) + 2 * j < V)) ? 1u << (2 * k + j) : 0u;
         const auto v2 = __builtin_amdgcn_raw_buffer_load_b64(rs, off, 0, 0);
         st[k][2 * j] = __builtin_bit_cast(float, (unsigned)v2[0]);
         st[k][2 * j + 1] = __builtin_bit_cast(float, (unsigned)v2[1]);
@@ -1701,59 +1770,111 @@ __global__ __launch_bounds__(512, 1) void k_wgrad_x3(WgradParams p) {
     }
   };
   static_assert(V % 2 == 0 && (G::ROWS * G::PG) % 64 == 0, "pair loads, uniform P/Q waves");
-  // splits and writes staging groups [K0, K1) of the loaded item
-  auto write_part = [&](char *buf, auto k0_c, auto k1_c) __attribute__((always_inline)) {
+  // splits one 4-joint group (scaled by sc at NPL = 2) and writes it to its planes
+  auto put_group = [&](char *dst, int pl, const float (&xv)[4], float sc)
+      __attribute__((always_inline)) {
+    if constexpr (NPL == 2) {
+      uint2 h, l;
+      splith2(xv[0] * sc, xv[1] * sc, h.x, l.x);
+      splith2(xv[2] * sc, xv[3] * sc, h.y, l.y);
+      *reinterpret_cast<uint2 *>(dst) = h;
+      *reinterpret_cast<uint2 *>(dst + pl) = l;
+    } else {
+      uint2 h, m, l;
+      split2(xv[0], xv[1], h.x, m.x, l.x);
+      split2(xv[2], xv[3], h.y, m.y, l.y);
+      *reinterpret_cast<uint2 *>(dst) = h;
+      *reinterpret_cast<uint2 *>(dst + pl) = m;
+      *reinterpret_cast<uint2 *>(dst + 2 * pl) = l;
+    }
+  };
+  // splits and writes staging groups [K0, K1) of the loaded item: P into the
+  // buffer pbuf, Q's new frames into the ring slots of that item's phase ph
+  auto write_part = [&](char *pbuf, int ph, auto k0_c, auto k1_c) __attribute__((always_inline)) {
     constexpr int K0 = decltype(k0_c)::value, K1 = decltype(k1_c)::value;
 #pragma unroll
     for (int k = K0; k < K1; ++k)
       if (gl[k] >= 0) {
-        char *dst = buf + (isq[k] ? NPL * G::PPL : 0) + gl[k];
+        char *dst = isq[k] ? qring + gl[k] + G::slot(ph, G::OLDF + gfr(k)) * (G::Vp * 2)
+                           : pbuf + gl[k];
         const int pl = isq[k] ? G::QPL : G::PPL;
-        if constexpr (NPL == 2) {
-          const float sc = isq[k] ? q_scale : p_scale;
-          float xv[4] = {st[k][0], st[k][1], st[k][2], st[k][3]};
-          if constexpr (QBN) {  // BN1(x) of a Q group's channel, 0 outside the clip
-            // (the P / Q split of the groups falls on wave boundaries: a scalar branch)
-            if (__builtin_amdgcn_readfirstlane((int)isq[k]) != 0) {
-              const float4 t = *reinterpret_cast<const float4 *>(qtab + 4 * grow[k]);
+        const float sc = isq[k] ? q_scale : p_scale;
+        float xv[4] = {st[k][0], st[k][1], st[k][2], st[k][3]};
+        if constexpr (QBN) {  // BN1(x) of a Q group's channel, 0 outside the clip
+          // (the P / Q split of the groups falls on wave boundaries: a scalar branch)
+          if (__builtin_amdgcn_readfirstlane((int)isq[k]) != 0) {
+            const float4 t = *reinterpret_cast<const float4 *>(qtab + 4 * grow(k));
 #pragma unroll
-              for (int e = 0; e < 4; ++e)
-                xv[e] = (qval >> (2 * k + e / 2)) & 1u ? (xv[e] - t.x) * t.y + t.z : 0.f;
-            }
+            for (int e = 0; e < 4; ++e)
+              xv[e] = (qval >> (2 * k + e / 2)) & 1u ? (xv[e] - t.x) * t.y + t.z : 0.f;
           }
-          uint2 h, l;
-          splith2(xv[0] * sc, xv[1] * sc, h.x, l.x);
-          splith2(xv[2] * sc, xv[3] * sc, h.y, l.y);
-          *reinterpret_cast<uint2 *>(dst) = h;
-          *reinterpret_cast<uint2 *>(dst + pl) = l;
-        } else {
-          uint2 h, m, l;
-          split2(st[k][0], st[k][1], h.x, m.x, l.x);
-          split2(st[k][2], st[k][3], h.y, m.y, l.y);
-          *reinterpret_cast<uint2 *>(dst) = h;
-          *reinterpret_cast<uint2 *>(dst + pl) = m;
-          *reinterpret_cast<uint2 *>(dst + 2 * pl) = l;
         }
+        put_group(dst, pl, xv, sc);
       }
   };
-  auto write_item = [&](char *buf) __attribute__((always_inline)) {
+  auto write_item = [&](char *pbuf, int ph) __attribute__((always_inline)) {
     // (in parts of three groups: one loop over all of them is not unrolled at every
     // instance -- the staging registers then go to scratch memory)
     using std::integral_constant;
     constexpr int Q = G::GPT;
     static_assert(Q <= 12, "write_item parts");
-    write_part(buf, integral_constant<int, 0>{}, integral_constant<int, (Q < 3 ? Q : 3)>{});
+    write_part(pbuf, ph, integral_constant<int, 0>{}, integral_constant<int, (Q < 3 ? Q : 3)>{});
     if constexpr (Q > 3)
-      write_part(buf, integral_constant<int, 3>{}, integral_constant<int, (Q < 6 ? Q : 6)>{});
+      write_part(pbuf, ph, integral_constant<int, 3>{}, integral_constant<int, (Q < 6 ? Q : 6)>{});
     if constexpr (Q > 6)
-      write_part(buf, integral_constant<int, 6>{}, integral_constant<int, (Q < 9 ? Q : 9)>{});
+      write_part(pbuf, ph, integral_constant<int, 6>{}, integral_constant<int, (Q < 9 ? Q : 9)>{});
     if constexpr (Q > 9)
-      write_part(buf, integral_constant<int, 9>{}, integral_constant<int, Q>{});
+      write_part(pbuf, ph, integral_constant<int, 9>{}, integral_constant<int, Q>{});
+  };
+  // refill: the OLDF frames of an item's window that no earlier item left in
+  // the ring (the split's first item, a clip start), loaded ...
+  float fo[G::OGPT][4];
+  unsigned fval = 0;  // QBN: as qval, of the refill's groups
+  auto fill_load = [&](int item) __attribute__((always_inline)) {
+    if constexpr (QBN) fval = 0;
+    const int n = item / p.n_mtiles, m0 = (item - n * p.n_mtiles) * G::FT;
+    const __amdgpu_buffer_rsrc_t rq = make_rsrc(p.Q + (int64_t)n * p.q_bstride, p.q_bstride);
+#pragma unroll
+    for (int k = 0; k < G::OGPT; ++k) {
+      const int e = k * 512 + tid, row = e / G::OG, g = e - row * G::OG;
+      const int fr = g / G::G4, v0 = (g % G::G4) * 4;
+      const int c = c0 + row, t = SIN * m0 + p.off + fr;
+      const bool ok = e < G::CB * G::OG && c < p.C && t >= 0 && t < p.T_src;
+      const unsigned base = ok ? (unsigned)(c * TV + t * V + v0) * 4u : kOOB;
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const unsigned off = v0 + 2 * j < V ? base + 8u * j : kOOB;
+        if constexpr (QBN) fval |= (ok && v0 + 2 * j < V) ? 1u << (2 * k + j) : 0u;
+        const auto v2 = __builtin_amdgcn_raw_buffer_load_b64(rq, off, 0, 0);
+        fo[k][2 * j] = __builtin_bit_cast(float, (unsigned)v2[0]);
+        fo[k][2 * j + 1] = __builtin_bit_cast(float, (unsigned)v2[1]);
+      }
+    }
+  };
+  // ... and written to the slots of window frames 0..OLDF-1 at the item's phase ph
+  auto fill_write = [&](int ph) __attribute__((always_inline)) {
+#pragma unroll
+    for (int k = 0; k < G::OGPT; ++k) {
+      const int e = k * 512 + tid, row = e / G::OG, g = e - row * G::OG;
+      const int fr = g / G::G4, v0 = (g % G::G4) * 4;
+      if (e < G::CB * G::OG) {
+        float xv[4] = {fo[k][0], fo[k][1], fo[k][2], fo[k][3]};
+        if constexpr (QBN) {
+          const float4 t = *reinterpret_cast<const float4 *>(qtab + 4 * row);
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+            xv[i] = (fval >> (2 * k + i / 2)) & 1u ? (xv[i] - t.x) * t.y + t.z : 0.f;
+        }
+        put_group(qring + (row * G::QPITCH + G::slot(ph, fr) * G::Vp + v0) * 2, G::QPL, xv,
+                  q_scale);
+      }
+    }
   };
 
-  // lane bases (elements) of the A (P) and B (Q) fragments in plane 0
+  // lane base (elements) of the A (P) fragments in plane 0, and the part of the
+  // B (Q) fragments' that does not move with the ring
   const int pa = (mi * 32 + lo) * G::PPITCH + hi * G::HF * G::Vp;
-  const int qb = lo * G::QPITCH + hi * SIN * G::HF * G::Vp + q0 * G::Vp;
+  const int qb = lo * G::QPITCH;
 
   auto run = [&](auto nt_c) __attribute__((always_inline)) {
     constexpr int NT = decltype(nt_c)::value;
@@ -1774,12 +1895,14 @@ __global__ __launch_bounds__(512, 1) void k_wgrad_x3(WgradParams p) {
     struct Frag {
       bf16x8_t a[MR][NPL], b[NPL][NT];
     };
+    // B lane bases of the current item (elements, plane 0): base ci = G::bidx(frame
+    // of the lane half, tap of the group) holds window frame G::bframe(ci, q0, hi)
+    constexpr int NB = SIN + NT;
+    int qbs[NB];
     auto ld = [&](const char *buf, int s, Frag &f) __attribute__((always_inline)) {
       const __bf16 *P = reinterpret_cast<const __bf16 *>(buf) + pa + 8 * s;
       const int ga = 2 * s, gb = 2 * s + 1;
-      const int oa = SIN * (ga / G::G4) * G::Vp + (ga % G::G4) * 4;
-      const int ob = SIN * (gb / G::G4) * G::Vp + (gb % G::G4) * 4;
-      const __bf16 *Q = reinterpret_cast<const __bf16 *>(buf + NPL * G::PPL) + qb;
+      const __bf16 *Q = reinterpret_cast<const __bf16 *>(qring);
 #pragma unroll
       for (int pl = 0; pl < NPL; ++pl) {
 #pragma unroll
@@ -1787,9 +1910,10 @@ __global__ __launch_bounds__(512, 1) void k_wgrad_x3(WgradParams p) {
           f.a[mb][pl] = *reinterpret_cast<const bf16x8_t *>(P + pl * (G::PPL / 2) + mb * 64 * G::PPITCH);
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
-          const __bf16 *Qp = Q + pl * (G::QPL / 2) + t * G::Vp;
-          const bf16x4_t b0 = *reinterpret_cast<const bf16x4_t *>(Qp + oa);
-          const bf16x4_t b1 = *reinterpret_cast<const bf16x4_t *>(Qp + ob);
+          const __bf16 *Qa = Q + qbs[G::bidx(ga / G::G4, t)] + pl * (G::QPL / 2) + (ga % G::G4) * 4;
+          const __bf16 *Qb = Q + qbs[G::bidx(gb / G::G4, t)] + pl * (G::QPL / 2) + (gb % G::G4) * 4;
+          const bf16x4_t b0 = *reinterpret_cast<const bf16x4_t *>(Qa);
+          const bf16x4_t b1 = *reinterpret_cast<const bf16x4_t *>(Qb);
           f.b[pl][t] = __builtin_shufflevector(b0, b1, 0, 1, 2, 3, 4, 5, 6, 7);
         }
       }
@@ -1822,42 +1946,55 @@ __global__ __launch_bounds__(512, 1) void k_wgrad_x3(WgradParams p) {
       }
     };
     Frag f[2];
+    int ph = 0;  // ring phase of the current item
     for (int it = it0; it < it1; ++it) {
-      const char *cur = lds + (G::NBUF == 2 ? ((it - it0) & 1) * G::BUF : 0);
-      char *nxt = lds + (G::NBUF == 2 ? ((it - it0 + 1) & 1) * G::BUF : 0);
-      // next item (the last iteration reloads its own item into the idle buffer:
-      // unconditional, so no register copies across the loop)
+      const char *cur = lds + ((it - it0) & 1) * G::PBUF;
+      char *nxt = lds + ((it - it0 + 1) & 1) * G::PBUF;
+      const int phn = G::next_phase(ph);
+      // the ring holds nothing of this item's first OLDF frames: the split's first
+      // item, a clip start. Their loads go out ahead of the next item's; their
+      // slots are free (the previous item's barrier), their writes get a barrier
+      // of their own. The item's NEWF last frames came the usual way.
+      const bool refill = it == it0 || it % p.n_mtiles == 0;
+      if (refill) fill_load(it);
+      // next item (the last iteration reloads its own item into the idle buffer
+      // and the ring's idle slots: unconditional, so no register copies across
+      // the loop)
       load_item(it + 1 < it1 ? it + 1 : it);
+      if (refill) {
+        fill_write(ph);
+        __syncthreads();
+      }
+#pragma unroll
+      for (int ci = 0; ci < NB; ++ci)
+        qbs[ci] = qb + G::slot(ph, G::bframe(ci, q0, hi)) * G::Vp;
       ld(cur, 0, f[0]);
 #pragma unroll
       for (int s = 0; s < G::KSTEPS; ++s) {
         if (s + 1 < G::KSTEPS) ld(cur, s + 1, f[(s + 1) & 1]);
         mm(f[s & 1]);
-        if constexpr (G::NBUF == 2 && kWgWriteStart < G::KSTEPS) {
+        if constexpr (kWgWriteStart < G::KSTEPS) {
           // double buffer: the next item's split + LDS writes ride in the MFMA
           // shadow of k-steps WSTART.. (the loads were issued at the item start)
           using std::integral_constant;
           constexpr int W0 = kWgWriteStart, NP = G::KSTEPS - W0, Q = G::GPT;
           static_assert(W0 >= 1 && NP >= 1 && NP <= 4, "write parts");
           if (s == W0)
-            write_part(nxt, integral_constant<int, 0>{}, integral_constant<int, Q / NP>{});
+            write_part(nxt, phn, integral_constant<int, 0>{}, integral_constant<int, Q / NP>{});
           else if (NP >= 2 && s == W0 + 1)
-            write_part(nxt, integral_constant<int, Q / NP>{}, integral_constant<int, 2 * Q / NP>{});
+            write_part(nxt, phn, integral_constant<int, Q / NP>{},
+                       integral_constant<int, 2 * Q / NP>{});
           else if (NP >= 3 && s == W0 + 2)
-            write_part(nxt, integral_constant<int, 2 * Q / NP>{},
+            write_part(nxt, phn, integral_constant<int, 2 * Q / NP>{},
                        integral_constant<int, 3 * Q / NP>{});
           else if (NP >= 4 && s == W0 + 3)
-            write_part(nxt, integral_constant<int, 3 * Q / NP>{}, integral_constant<int, Q>{});
+            write_part(nxt, phn, integral_constant<int, 3 * Q / NP>{}, integral_constant<int, Q>{});
         }
         __builtin_amdgcn_sched_barrier(0);
       }
-      if constexpr (G::NBUF == 1) {
-        __syncthreads();  // every wave is done reading the buffer
-        write_item(nxt);
-      } else if constexpr (kWgWriteStart >= G::KSTEPS) {
-        write_item(nxt);
-      }
+      if constexpr (kWgWriteStart >= G::KSTEPS) write_item(nxt, phn);
       __syncthreads();
+      ph = phn;
     }
     // the tile [ROWS][CB channels][9 taps] through LDS (the staging buffers are
     // free after the last item's barrier), then whole 16-byte pieces of each
@@ -1898,9 +2035,9 @@ __global__ __launch_bounds__(512, 1) void k_wgrad_x3(WgradParams p) {
       }
     }
   };
-  if (it0 < it1) {
+  if (it0 < it1) {  // P and the new frames of the first item; the loop refills the rest
     load_item(it0);
-    write_item(lds);
+    write_item(lds, 0);
   }
   __syncthreads();
   if (tq == 0)
