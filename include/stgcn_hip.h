@@ -52,6 +52,9 @@
  *         8; stgcn_adam_*: the device table 8, every param / grad / exp_avg /
  *         exp_avg_sq and the device step 4 (views into a flat bucket work in
  *         place). These kernels access one element at a time.
+ *       STGCN_FEATURE_STEP_STATE: seed_dev (stgcn_block_fwd_dseed / _bwd_dseed)
+ *         and stgcn_seed_next's counter / token 8 (64-bit words); lr_dev,
+ *         grad_coef, norm_out, coef_out 4; stgcn_grad_norm's partials 8.
  *     A caller with a misaligned read-only input for a 16-byte argument passes an
  *     aligned copy (the Python binding does); torch.empty results are aligned.
  *   - A is (K,V,V), W is (K*C_out, C_in) (the reference's 1x1 Conv2d weight),
@@ -287,6 +290,9 @@ const char *stgcn_last_error(void);
  * an existing call does): */
 #define STGCN_FEATURE_EVAL_CHAIN 1 /* stgcn_block_fwd chains in eval (STGCN_PLAN_X_FROM_U_EVAL) */
 #define STGCN_FEATURE_EVAL_HEAD 2  /* stgcn_head_eval / _u and the metrics block           */
+#define STGCN_FEATURE_STEP_STATE 4 /* per-step values read from device memory: the _dseed
+                                    * block calls, stgcn_seed_next, stgcn_adam_step_dev2,
+                                    * stgcn_grad_norm                                     */
 int stgcn_features(void);
 
 /* Validate a descriptor without touching the GPU (0 = supported). */
@@ -301,6 +307,31 @@ int stgcn_block_fwd(const stgcn_desc_t *d, const stgcn_fwd_args_t *a,
                     void *workspace, size_t workspace_bytes, void *stream);
 int stgcn_block_bwd(const stgcn_desc_t *d, const stgcn_bwd_args_t *a,
                     void *workspace, size_t workspace_bytes, void *stream);
+
+/* STGCN_FEATURE_STEP_STATE: the block calls with the dropout's step token in
+ * device memory. Element e of the block output is kept iff
+ *     hi32(mix64(s + e * PHI)) >= dropout_p * 2^32,   PHI = 0x9E3779B97F4A7C15,
+ *     mix64(z): z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;
+ *               z = (z ^ z >> 27) * 0x94D049BB133111EB;  z ^ z >> 31   (mod 2^64)
+ * with s = a->seed for stgcn_block_fwd / _bwd and for seed_dev null (bit for bit
+ * the same call), else the effective seed
+ *     s = mix64(a->seed + c * PHI),   c = *seed_dev,
+ * read by each kernel when it RUNS: nothing about the mask is fixed when the call
+ * is enqueued, so a call captured in a HIP graph draws a new mask on every replay
+ * once the token advances (stgcn_seed_next). The hash is needed: with a plain
+ * a->seed + c * PHI the mask of token c + 1 is that of token c shifted by one
+ * element. The backward regenerates the mask and must see the value its forward
+ * saw: give each forward a token word of its own (stgcn_seed_next writes one)
+ * and pass that word to its backward. seed_dev: 8-byte aligned. */
+int stgcn_block_fwd_dseed(const stgcn_desc_t *d, const stgcn_fwd_args_t *a,
+                          const uint64_t *seed_dev, void *workspace, size_t workspace_bytes,
+                          void *stream);
+int stgcn_block_bwd_dseed(const stgcn_desc_t *d, const stgcn_bwd_args_t *a,
+                          const uint64_t *seed_dev, void *workspace, size_t workspace_bytes,
+                          void *stream);
+/* *counter += 1; *token = *counter, on the stream (one thread): the token of
+ * the next forward. counter and token: device words, 8-byte aligned. */
+int stgcn_seed_next(uint64_t *counter, uint64_t *token, void *stream);
 
 /* ---------------------------------------------------------------------------
  * ABI 4: SpatialConv on its own (st_graphconv.py:139-152):
@@ -506,6 +537,26 @@ int stgcn_adam_step(const void *dev_table, int ntensors, int64_t total_chunks, d
 int stgcn_adam_step_dev(const void *dev_table, int ntensors, int64_t total_chunks, double lr,
                         double beta1, double beta2, double eps, double weight_decay, float *step,
                         void *stream);
+/* STGCN_FEATURE_STEP_STATE: stgcn_adam_step_dev with the learning rate read from
+ * device memory when the kernel runs (lr_dev, a float: a scheduler writes it
+ * between replays of a captured step; -lr / bc1 is formed as (float)(-((double)
+ * *lr_dev / bc1))), and an optional gradient scale grad_coef (a device float, or
+ * null): g = grad * *grad_coef before the weight-decay term, which is where
+ * torch.nn.utils.clip_grad_norm_ before step() puts it. The gradients themselves
+ * are not rewritten. */
+int stgcn_adam_step_dev2(const void *dev_table, int ntensors, int64_t total_chunks,
+                         const float *lr_dev, const float *grad_coef, double beta1, double beta2,
+                         double eps, double weight_decay, float *step, void *stream);
+/* The 2-norm of every gradient of an Adam table and the clip coefficient of
+ * clip_grad_norm_: one fp64 sum of squares per table chunk into partials
+ * (stgcn_grad_norm_bytes(total_chunks) bytes, plain stores), then one workgroup
+ * adds the partials in a fixed order and writes *norm_out = (float)sqrt(sum) and
+ * *coef_out = min(1, max_norm / (*norm_out + 1e-6)) in float. No atomics: the
+ * same gradients give the same bits. (One norm over several parameter groups:
+ * a table of all their tensors; only grad and numel of each entry are read.) */
+size_t stgcn_grad_norm_bytes(int64_t total_chunks);
+int stgcn_grad_norm(const void *dev_table, int ntensors, int64_t total_chunks, double max_norm,
+                    double *partials, float *norm_out, float *coef_out, void *stream);
 
 #ifdef __cplusplus
 }

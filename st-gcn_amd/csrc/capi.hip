@@ -82,10 +82,12 @@ size_t y_stats_bytes(int C) {
 static_assert(STGCN_STATS_AMAX_WORDS == kAmaxWords, "ABI 7: the amax block of y_stats");
 
 // the fused dropout of a call (training and 0 < p < 1; p >= 1: everything dropped)
-Dropout make_dropout(const stgcn_desc_t *d, float p, uint64_t seed) {
+// (seed_dev: the step token of the _dseed entry points, internal.h Dropout)
+Dropout make_dropout(const stgcn_desc_t *d, float p, uint64_t seed, const uint64_t *seed_dev) {
   Dropout dr;
   if (!d->training || !(p > 0.f)) return dr;
   dr.seed = seed;
+  dr.seed_dev = seed_dev;
   const double t = (double)p * 4294967296.0;
   dr.thresh = t >= 4294967295.0 ? 0xffffffffu : (uint32_t)t;
   dr.scale = p < 1.f ? (float)(1.0 / (1.0 - (double)p)) : 0.f;
@@ -260,6 +262,7 @@ struct FwdCtx {
   bool no_memset;
   float *mean1, *invstd1, *mean2, *invstd2;
   const unsigned *xmax = nullptr;  // (bna: max |x|, the fp16 operand bound's input)
+  const uint64_t *seed_dev = nullptr;  // the dropout's step token (stgcn_block_fwd_dseed)
   const float *Gfold = nullptr;    // the folded block's G (spatial stage -> temporal stage)
 };
 
@@ -407,7 +410,7 @@ int residual_fwd_tail(FwdCtx &c) {
   p.bias_r = a->bWt;
   p.res = resid;
   p.relu_out = 1;
-  p.drop = make_dropout(d, a->dropout_p, a->seed);
+  p.drop = make_dropout(d, a->dropout_p, a->seed, c.seed_dev);
   if (d->training && a->y_stats) {  // next block's BN1 statistics from the epilogue
     HIP_TRY(hipMemsetAsync(a->y_stats, 0, y_stats_bytes(R), s));
     p.stat_sum = a->y_stats;
@@ -507,7 +510,7 @@ int fwd_bn2_out(FwdCtx &c) {
   else
     HIP_TRY(launch_bn_finalize(L.s2, L.q2, R, (int64_t)N * To * V, d->eps, d->momentum,
                                d->training, a->rm2, a->rv2, c.mean2, c.invstd2, s));
-  const Dropout ydrop = make_dropout(d, a->dropout_p, a->seed);
+  const Dropout ydrop = make_dropout(d, a->dropout_p, a->seed, c.seed_dev);
   // (ABI 5: y_stats holds 5 * C_out sums; the last three -- over the ReLU mask --
   // feed the next block's deferred-dx chain, meaningless under dropout; ABI 7:
   // then max y in STGCN_STATS_AMAX_WORDS words, the next block's operand bound;
@@ -526,9 +529,17 @@ int fwd_bn2_out(FwdCtx &c) {
 
 extern "C" int stgcn_block_fwd(const stgcn_desc_t *d, const stgcn_fwd_args_t *a, void *workspace,
                                size_t workspace_bytes, void *stream) {
+  return stgcn_block_fwd_dseed(d, a, nullptr, workspace, workspace_bytes, stream);
+}
+
+extern "C" int stgcn_block_fwd_dseed(const stgcn_desc_t *d, const stgcn_fwd_args_t *a,
+                                     const uint64_t *seed_dev, void *workspace,
+                                     size_t workspace_bytes, void *stream) {
   STAGE(stgcn_check_desc(d));
+  STAGE(check_aligned({NamedPtr{seed_dev, "seed_dev"}}, 8));
   STAGE(fwd_check_args(d, a, workspace));
   FwdCtx c{d, a, fwd_layout(d, workspace), (hipStream_t)stream};
+  c.seed_dev = seed_dev;
   if (!workspace || workspace_bytes < c.L.total)
     return fail(STGCN_E_INVALID, "workspace too small");
   c.res = residual(d);
@@ -592,7 +603,7 @@ int bwd_check_args(const stgcn_desc_t *d, const stgcn_bwd_args_t *a, void *works
   // the frame-wise dU A pass of the block without G)
   if (a->dy_nc && (res || (cols_sums(d) && fold_bna(d))))
     return fail(STGCN_E_UNSUPPORTED, "dy_nc: this block's backward needs the full dy");
-  const Dropout drop = make_dropout(d, a->dropout_p, a->seed);
+  const Dropout drop = make_dropout(d, a->dropout_p, a->seed, nullptr);
   if (drop.thresh && a->dy_sums)
     return fail(STGCN_E_INVALID, "dy_sums cannot be combined with dropout");
   if (!d->training && (a->dy_sums || a->prev_sums))
@@ -962,13 +973,20 @@ int bwd_bn1_tail(BwdCtx &c) {
 
 extern "C" int stgcn_block_bwd(const stgcn_desc_t *d, const stgcn_bwd_args_t *a, void *workspace,
                                size_t workspace_bytes, void *stream) {
+  return stgcn_block_bwd_dseed(d, a, nullptr, workspace, workspace_bytes, stream);
+}
+
+extern "C" int stgcn_block_bwd_dseed(const stgcn_desc_t *d, const stgcn_bwd_args_t *a,
+                                     const uint64_t *seed_dev, void *workspace,
+                                     size_t workspace_bytes, void *stream) {
   STAGE(stgcn_check_desc(d));
+  STAGE(check_aligned({NamedPtr{seed_dev, "seed_dev"}}, 8));
   STAGE(bwd_check_args(d, a, workspace));
   BwdCtx c{d, a, bwd_layout(d, workspace), (hipStream_t)stream};
   if (!workspace || workspace_bytes < c.L.total)
     return fail(STGCN_E_INVALID, "workspace too small");
   c.res = residual(d);
-  c.drop = make_dropout(d, a->dropout_p, a->seed);
+  c.drop = make_dropout(d, a->dropout_p, a->seed, seed_dev);
   const int N = d->N, C = d->C_in, R = d->C_out, T = d->T, V = d->V, K = d->K;
   c.mean1 = a->stats;
   c.invstd1 = a->stats + C;

@@ -215,8 +215,13 @@ __device__ __forceinline__ void conv_tile_epilogue(const ConvGemmParams &p, floa
       }
     }
   };
-  auto epilogue = [&](auto stats_c) {
+  // (DROP: a compile-time copy of the loop for calls with dropout, so the copy
+  // every other call runs holds no seed and has no dropout branch)
+  auto epilogue = [&](auto stats_c, auto drop_c) {
     constexpr bool STATS = decltype(stats_c)::value;
+    constexpr bool DROP = decltype(drop_c)::value;
+    Dropout drop;
+    if constexpr (DROP) drop = dropout_resolve(p.drop);
     double *red = reinterpret_cast<double *>(smem);  // [4 waves][2 halves][32]
     Pre pf[PF ? 2 : 1];
     if constexpr (PF) prefetch(0, pf[0]);
@@ -258,10 +263,12 @@ __device__ __forceinline__ void conv_tile_epilogue(const ConvGemmParams &p, floa
           else if (p.res)
             val += __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_res, off, 0, 0));
           if (p.relu_out) val = fmaxf(val, 0.f);
-          if (p.drop.thresh && ok)
-            val = dropout_keep(p.drop, (uint64_t)n * p.out_bstride + row * ostride + ocol[j])
-                      ? val * p.drop.scale
-                      : 0.f;
+          if constexpr (DROP) {
+            if (ok)
+              val = dropout_keep(drop, (uint64_t)n * p.out_bstride + row * ostride + ocol[j])
+                        ? val * drop.scale
+                        : 0.f;
+          }
           if (ob)
             __builtin_amdgcn_raw_buffer_store_b16(
                 __builtin_bit_cast(unsigned short, (__bf16)val), rs_o,
@@ -309,10 +316,16 @@ __device__ __forceinline__ void conv_tile_epilogue(const ConvGemmParams &p, floa
       }
     }
   };
-  if (p.stat_sum)
-    epilogue(std::true_type{});
-  else
-    epilogue(std::false_type{});
+  if (p.drop.thresh) {  // (uniform)
+    if (p.stat_sum)
+      epilogue(std::true_type{}, std::true_type{});
+    else
+      epilogue(std::false_type{}, std::true_type{});
+  } else if (p.stat_sum) {
+    epilogue(std::true_type{}, std::false_type{});
+  } else {
+    epilogue(std::false_type{}, std::false_type{});
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -342,9 +355,11 @@ __device__ __forceinline__ void acc_to_img(float *img, const floatx16 &a, int ro
 // PF: every residual / bias-table load hoisted ahead of the stores (below);
 // costs 4 PPT registers -- for one-workgroup-per-CU kernels only (at two per CU
 // the extra registers halved the occupancy: +37% on the bf16 k_conv_x3)
-template <int V, int NCOLS, int NT, int ROWS = 64, bool OB = false, bool PF = false>
-__device__ __forceinline__ void conv_tile_store_rows(const ConvGemmParams &p, const float *img,
-                                                     float *sbv, int n, int r0, int m0) {
+// (DROP: conv_tile_store_rows below picks the copy with the dropout for calls
+// that have one; the copy every other call runs holds no seed and no branch)
+template <int V, int NCOLS, int NT, int ROWS, bool OB, bool PF, bool DROP>
+__device__ __forceinline__ void conv_tile_store_rows_t(const ConvGemmParams &p, const float *img,
+                                                       float *sbv, int n, int r0, int m0) {
   constexpr int TPR = NT / ROWS;
   static_assert(TPR >= 1 && NT % ROWS == 0, "whole threads per row");
   constexpr int NP = (NCOLS + 3) / 4;  // 16-byte pieces per row
@@ -355,6 +370,8 @@ __device__ __forceinline__ void conv_tile_store_rows(const ConvGemmParams &p, co
   const bool rok = row < p.R;
   const int ostride = p.T_dst * V;
   const int ncv = min(NCOLS, (p.M - m0) * V);  // valid columns of the tile
+  Dropout drop;
+  if constexpr (DROP) drop = dropout_resolve(p.drop);
   if (p.bias_rv) {  // the tile's rows of the bias table, coalesced (uniform branch)
     const int nrow = min(ROWS, p.R - r0);
     for (int i = tid; i < nrow * V; i += NT) sbv[i] = p.bias_rv[r0 * V + i];
@@ -424,8 +441,9 @@ __device__ __forceinline__ void conv_tile_store_rows(const ConvGemmParams &p, co
       if (p.bias_rv && ok) val += sbv[r * V + col % V];
       val += rv[e];
       if (p.relu_out) val = fmaxf(val, 0.f);
-      if (p.drop.thresh && ok)
-        val = dropout_keep(p.drop, (uint64_t)(obase + col)) ? val * p.drop.scale : 0.f;
+      if constexpr (DROP) {
+        if (ok) val = dropout_keep(drop, (uint64_t)(obase + col)) ? val * drop.scale : 0.f;
+      }
       v[e] = val;
       if (p.stat_sum && ok) {
         s += (double)val;
@@ -477,6 +495,15 @@ __device__ __forceinline__ void conv_tile_store_rows(const ConvGemmParams &p, co
       atomicAdd(p.stat_sq + row, sq);
     }
   }
+}
+
+template <int V, int NCOLS, int NT, int ROWS = 64, bool OB = false, bool PF = false>
+__device__ __forceinline__ void conv_tile_store_rows(const ConvGemmParams &p, const float *img,
+                                                     float *sbv, int n, int r0, int m0) {
+  if (p.drop.thresh)  // (uniform)
+    conv_tile_store_rows_t<V, NCOLS, NT, ROWS, OB, PF, true>(p, img, sbv, n, r0, m0);
+  else
+    conv_tile_store_rows_t<V, NCOLS, NT, ROWS, OB, PF, false>(p, img, sbv, n, r0, m0);
 }
 
 }  // namespace stgcn

@@ -11,18 +11,41 @@ namespace stgcn {
 // scaled by 1/(1-p). thresh == 0: no dropout. The hash (splitmix64 of
 // seed + e * golden ratio) is counter-based: the backward regenerates the
 // mask instead of storing it.
+//
+// seed_dev (or null; STGCN_FEATURE_STEP_STATE): a 64-bit device word c, the
+// step token. The mask then uses the effective seed
+//     seed' = mix64(seed + c * golden ratio)
+// read when the kernel runs, so a captured graph draws a new mask per replay
+// (stgcn_seed_next advances the token on the stream). The hash matters: with a
+// plain seed + c * golden ratio, step c + 1's mask is step c's shifted by one
+// element.
 struct Dropout {
   uint64_t seed = 0;
   uint32_t thresh = 0;
   float scale = 1.f;
+  const uint64_t *seed_dev = nullptr;
 };
 
-__host__ __device__ inline bool dropout_keep(const Dropout &d, uint64_t e) {
-  uint64_t z = d.seed + e * 0x9E3779B97F4A7C15ull;
+constexpr uint64_t kDropGolden = 0x9E3779B97F4A7C15ull;
+
+// the splitmix64 finaliser
+__host__ __device__ inline uint64_t mix64(uint64_t z) {
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
   z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  z ^= z >> 31;
-  return (uint32_t)(z >> 32) >= d.thresh;
+  return z ^ (z >> 31);
+}
+
+__host__ __device__ inline bool dropout_keep(const Dropout &d, uint64_t e) {
+  return (uint32_t)(mix64(d.seed + e * kDropGolden) >> 32) >= d.thresh;
+}
+
+// The Dropout a kernel works with: the step token folded into the seed, once
+// at kernel entry (one uniform load and one mix64, not one per element). Every
+// kernel that takes a Dropout calls this before its first dropout_keep.
+__device__ __forceinline__ Dropout dropout_resolve(Dropout d) {
+  if (d.thresh && d.seed_dev) d.seed = mix64(d.seed + *d.seed_dev * kDropGolden);
+  d.seed_dev = nullptr;
+  return d;
 }
 
 // Deferred-dx chain (ABI 5; capi.hip "deferred dx"): the spatial backward of

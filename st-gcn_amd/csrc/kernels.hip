@@ -192,35 +192,46 @@ __global__ __launch_bounds__(256, 2) void k_conv_gemm(ConvGemmParams p) {
       }
     }
   };
-  pre(0, pbv[0], prs[0]);
+  // (DROP: a compile-time copy of the loop for calls with dropout, so the copy
+  // every other call runs holds no seed and has no dropout branch)
+  auto rows = [&](auto drop_c) {
+    constexpr bool DROP = decltype(drop_c)::value;
+    Dropout drop;
+    if constexpr (DROP) drop = dropout_resolve(p.drop);
+    pre(0, pbv[0], prs[0]);
 #pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    if (i + 1 < 16) pre(i + 1, pbv[(i + 1) & 1], prs[(i + 1) & 1]);
-    const int row = r0 + mi * 32 + (i & 3) + 8 * (i >> 2) + 4 * hi;
-    const bool rok = row < p.R;
-    const float br = brv[i];
-    double s = 0.0, sq = 0.0;
+    for (int i = 0; i < 16; ++i) {
+      if (i + 1 < 16) pre(i + 1, pbv[(i + 1) & 1], prs[(i + 1) & 1]);
+      const int row = r0 + mi * 32 + (i & 3) + 8 * (i >> 2) + 4 * hi;
+      const bool rok = row < p.R;
+      const float br = brv[i];
+      double s = 0.0, sq = 0.0;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      if (rok && cok[j]) {
-        float val = acc[j][i] + br;
-        if (p.bias_rv) val += pbv[i & 1][j];
-        if (p.res) val += prs[i & 1][j];
-        if (p.relu_out) val = fmaxf(val, 0.f);
-        if (p.drop.thresh)
-          val = dropout_keep(p.drop, (uint64_t)n * p.out_bstride + row * ostride + ocol[j])
-                    ? val * p.drop.scale
-                    : 0.f;
-        outN[row * ostride + ocol[j]] = val;
-        s += val;
-        sq += (double)val * val;
+      for (int j = 0; j < 4; ++j) {
+        if (rok && cok[j]) {
+          float val = acc[j][i] + br;
+          if (p.bias_rv) val += pbv[i & 1][j];
+          if (p.res) val += prs[i & 1][j];
+          if (p.relu_out) val = fmaxf(val, 0.f);
+          if constexpr (DROP)
+            val = dropout_keep(drop, (uint64_t)n * p.out_bstride + row * ostride + ocol[j])
+                      ? val * drop.scale
+                      : 0.f;
+          outN[row * ostride + ocol[j]] = val;
+          s += val;
+          sq += (double)val * val;
+        }
+      }
+      if (p.stat_sum) {
+        red[((wave * 16 + i) * 2 + 0) * 64 + lane] = s;
+        red[((wave * 16 + i) * 2 + 1) * 64 + lane] = sq;
       }
     }
-    if (p.stat_sum) {
-      red[((wave * 16 + i) * 2 + 0) * 64 + lane] = s;
-      red[((wave * 16 + i) * 2 + 1) * 64 + lane] = sq;
-    }
-  }
+  };
+  if (p.drop.thresh)  // (uniform)
+    rows(std::true_type{});
+  else
+    rows(std::false_type{});
   if (p.stat_sum) {
     __syncthreads();
     if (tid < 128) {
@@ -1520,6 +1531,7 @@ __device__ __forceinline__ void bn_relu_fwd_body(const float *U, const float *me
                                                  double *ysum, double *ysq, Dropout drop,
                                                  double *yext, unsigned *ymax) {
   __shared__ double red[8];
+  drop = dropout_resolve(drop);
   const int c = blockIdx.x, n0 = blockIdx.y * kBnRows, n1 = min(N, n0 + kBnRows);
   const float mu = mean[c], is = invstd[c], a = is * g[c], be = b[c];
   double s = 0.0, q = 0.0, cnt = 0.0, su = 0.0, xu = 0.0;
@@ -1615,6 +1627,7 @@ __global__ __launch_bounds__(256) void k_bn_relu_bwd_reduce(const float *dy, con
   const int64_t base = ((int64_t)n * C + c) * L;
   const float mu = mean[c], is = invstd[c], a = is * g[c], be = b[c];
   const float dv = dync ? dync[(int64_t)n * C + c] : 0.f;  // (ABI 10: dy constant per row)
+  drop = dropout_resolve(drop);
   double s = 0.0, q = 0.0;
   for (int i = threadIdx.x * VEC; i < L; i += 256 * VEC) {
     float u[VEC], d[VEC];
@@ -1659,6 +1672,7 @@ __global__ __launch_bounds__(256) void k_bn_relu_bwd_apply(
   const int c = blockIdx.x, n = blockIdx.y;
   const int64_t base = ((int64_t)n * C + c) * L;
   const float dv = dync ? dync[(int64_t)n * C + c] : 0.f;  // (ABI 10: dy constant per row)
+  drop = dropout_resolve(drop);
   const float mu = mean[c], is = invstd[c], a = is * g[c], be = b[c];
   const float mg = (float)(sg[c] * invM), mgu = (float)(sgu[c] * invM);
   // deferred dx of the next block: dy = ca * (dxhat - cmd - (y - cmu) * cis * cmdn)
@@ -1746,6 +1760,7 @@ __global__ __launch_bounds__(256) void k_bn_relu_bwd_apply_cols(
     int du_bf16, const float *dy_coef, double *__restrict__ cs, unsigned *amax,
     const float *dync) {
   __shared__ double red[8];
+  drop = dropout_resolve(drop);
   float om = 0.f;  // max |dU| (f16x2 operand bound)
   const int c = blockIdx.x;
   const int i = (blockIdx.y * 256 + threadIdx.x) * VEC;
@@ -1873,6 +1888,7 @@ __global__ __launch_bounds__(256) void k_bn_relu_bwd_apply_fr(
   static_assert(NP / 2 <= 256 && NP <= 512, "one pair per thread, two outputs per thread");
   __shared__ float ob[2][NP];
   __shared__ double red[8];
+  drop = dropout_resolve(drop);
   const int tid = threadIdx.x;
   const int c = blockIdx.x;
   const int f0 = blockIdx.y * kFrTile, nf = min(kFrTile, To - f0);

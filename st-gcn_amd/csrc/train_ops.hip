@@ -68,10 +68,12 @@ struct AdamScalars {
   float lerp_w, beta2, one_minus_beta2, neg_step_size, bc2_sqrt, eps, wd;
 };
 
-// the element loop of both launch forms (one function: the same instructions)
+// the element loop of every launch form (one function: the same instructions)
+// COEF (k_adam_dev2 with a grad_coef): g = grad * coef ahead of the weight decay
+template <bool COEF = false>
 __device__ __forceinline__ void adam_block(const stgcn_adam_tensor_t *tab,
                                            const int64_t *chunk_start, int ntensors,
-                                           const AdamScalars &s) {
+                                           const AdamScalars &s, float coef = 1.f) {
 #pragma clang fp contract(off)
   // tensor of this block: the last t with chunk_start[t] <= blockIdx.x
   const int64_t b = blockIdx.x;
@@ -89,6 +91,7 @@ __device__ __forceinline__ void adam_block(const stgcn_adam_tensor_t *tab,
     // differed between the two kernels -- as torch's unfused CPU loop rounds)
     float p = t.param[e];
     float g = t.grad[e];
+    if constexpr (COEF) g = g * coef;
     if (s.wd != 0.f) g = g + s.wd * p;
     float m = t.exp_avg[e];
     m = m + s.lerp_w * (g - m);
@@ -135,6 +138,97 @@ __global__ __launch_bounds__(256) void k_adam_dev(const stgcn_adam_tensor_t *tab
   __syncthreads();
   const AdamScalars s = sh;
   adam_block(tab, chunk_start, ntensors, s);
+}
+
+// stgcn_adam_step_dev2 (STGCN_FEATURE_STEP_STATE): k_adam_dev with the learning
+// rate, and optionally a gradient scale, read from device memory, so a captured
+// step follows a scheduler and a clip coefficient without a re-capture.
+__global__ __launch_bounds__(256) void k_adam_dev2(const stgcn_adam_tensor_t *tab,
+                                                   const int64_t *chunk_start, int ntensors,
+                                                   const float *step, const float *lr_dev,
+                                                   const float *grad_coef, double beta1,
+                                                   double beta2, double eps, double wd) {
+  __shared__ AdamScalars sh;
+  __shared__ float sh_coef;
+  if (threadIdx.x == 0) {
+    const double t = (double)*step;
+    const double bc1 = 1.0 - pow(beta1, t), bc2 = 1.0 - pow(beta2, t);
+    AdamScalars sc;
+    sc.lerp_w = (float)(1.0 - beta1);
+    sc.beta2 = (float)beta2;
+    sc.one_minus_beta2 = (float)(1.0 - beta2);
+    sc.neg_step_size = (float)(-((double)*lr_dev / bc1));
+    sc.bc2_sqrt = (float)sqrt(bc2);
+    sc.eps = (float)eps;
+    sc.wd = (float)wd;
+    sh = sc;
+    sh_coef = grad_coef ? *grad_coef : 1.f;
+  }
+  __syncthreads();
+  const AdamScalars s = sh;
+  if (grad_coef)
+    adam_block<true>(tab, chunk_start, ntensors, s, sh_coef);
+  else
+    adam_block(tab, chunk_start, ntensors, s);
+}
+
+// The dropout step token (stgcn_seed_next), in k_adam_tick's style
+__global__ void k_seed_next(uint64_t *counter, uint64_t *token) {
+  *counter += 1;
+  *token = *counter;
+}
+
+// Gradient norm over an Adam table (stgcn_grad_norm). k_grad_sq: block b = chunk
+// b of the table (adam_block's chunking), its sum of grad^2 in fp64 -- per
+// thread in element order, then the block in a fixed tree -- stored to
+// partials[b]. k_grad_norm: one workgroup adds the partials (thread i takes
+// i, i + 256, ... in order; the same tree) and writes the norm and the clip
+// coefficient. Plain stores only: the result does not depend on scheduling.
+__device__ __forceinline__ double block_sum_fixed(double v, double *red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) red[wave] = v;
+  __syncthreads();
+  return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+__global__ __launch_bounds__(256) void k_grad_sq(const stgcn_adam_tensor_t *tab,
+                                                 const int64_t *chunk_start, int ntensors,
+                                                 double *partials) {
+  __shared__ double red[4];
+  const int64_t b = blockIdx.x;
+  int lo = 0, hi = ntensors - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (chunk_start[mid] <= b) lo = mid; else hi = mid - 1;
+  }
+  const float *grad = tab[lo].grad;
+  const int64_t numel = tab[lo].numel;
+  const int64_t base = (b - chunk_start[lo]) * kAdamChunk;
+  double s = 0.0;
+  for (int i = threadIdx.x; i < kAdamChunk; i += 256) {
+    const int64_t e = base + i;
+    if (e >= numel) break;
+    const double g = (double)grad[e];
+    s += g * g;
+  }
+  s = block_sum_fixed(s, red);
+  if (threadIdx.x == 0) partials[b] = s;
+}
+
+__global__ __launch_bounds__(256) void k_grad_norm(const double *partials, int64_t n,
+                                                   float max_norm, float *norm_out,
+                                                   float *coef_out) {
+  __shared__ double red[4];
+  double s = 0.0;
+  for (int64_t i = threadIdx.x; i < n; i += 256) s += partials[i];
+  s = block_sum_fixed(s, red);
+  if (threadIdx.x == 0) {
+    const float norm = (float)sqrt(s);
+    *norm_out = norm;
+    *coef_out = fminf(1.f, max_norm / (norm + 1e-6f));
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -513,6 +607,58 @@ int stgcn_adam_step_dev(const void *dev_table, int ntensors, int64_t total_chunk
   return STGCN_OK;
 }
 
+int stgcn_adam_step_dev2(const void *dev_table, int ntensors, int64_t total_chunks,
+                         const float *lr_dev, const float *grad_coef, double beta1, double beta2,
+                         double eps, double weight_decay, float *step, void *stream) {
+  if (!dev_table || ntensors <= 0 || total_chunks <= 0 || !step)
+    return fail(STGCN_E_INVALID, "adam: bad table / chunk count / step pointer");
+  if (!lr_dev) return fail(STGCN_E_INVALID, "adam: lr_dev is null");
+  if (int rc = check_aligned({NP(dev_table)}, 8)) return rc;
+  if (int rc = check_aligned({NP(step), NP(lr_dev), NP(grad_coef)}, 4)) return rc;
+  const auto *tab = reinterpret_cast<const stgcn_adam_tensor_t *>(dev_table);
+  const auto *cs = reinterpret_cast<const int64_t *>(reinterpret_cast<const char *>(dev_table) +
+                                                     (size_t)ntensors * sizeof(stgcn_adam_tensor_t));
+  hipLaunchKernelGGL(k_adam_tick, dim3(1), dim3(1), 0, (hipStream_t)stream, step);
+  hipLaunchKernelGGL(k_adam_dev2, dim3((unsigned)total_chunks), dim3(256), 0, (hipStream_t)stream,
+                     tab, cs, ntensors, step, lr_dev, grad_coef, beta1, beta2, eps, weight_decay);
+  HIP_TRY2(hipGetLastError());
+  return STGCN_OK;
+}
+
+size_t stgcn_grad_norm_bytes(int64_t total_chunks) {
+  return total_chunks > 0 ? (size_t)total_chunks * sizeof(double) : 0;
+}
+
+int stgcn_grad_norm(const void *dev_table, int ntensors, int64_t total_chunks, double max_norm,
+                    double *partials, float *norm_out, float *coef_out, void *stream) {
+  if (!dev_table || ntensors <= 0 || total_chunks <= 0 || total_chunks > INT32_MAX)
+    return fail(STGCN_E_INVALID, "grad_norm: bad table / chunk count");
+  if (!partials) return fail(STGCN_E_INVALID, "grad_norm: partials is null");
+  if (!norm_out) return fail(STGCN_E_INVALID, "grad_norm: norm_out is null");
+  if (!coef_out) return fail(STGCN_E_INVALID, "grad_norm: coef_out is null");
+  if (!(max_norm > 0.0)) return fail(STGCN_E_INVALID, "grad_norm: max_norm must be positive");
+  if (int rc = check_aligned({NP(dev_table), NP(partials)}, 8)) return rc;
+  if (int rc = check_aligned({NP(norm_out), NP(coef_out)}, 4)) return rc;
+  const auto *tab = reinterpret_cast<const stgcn_adam_tensor_t *>(dev_table);
+  const auto *cs = reinterpret_cast<const int64_t *>(reinterpret_cast<const char *>(dev_table) +
+                                                     (size_t)ntensors * sizeof(stgcn_adam_tensor_t));
+  hipLaunchKernelGGL(k_grad_sq, dim3((unsigned)total_chunks), dim3(256), 0, (hipStream_t)stream,
+                     tab, cs, ntensors, partials);
+  hipLaunchKernelGGL(k_grad_norm, dim3(1), dim3(256), 0, (hipStream_t)stream, partials,
+                     total_chunks, (float)max_norm, norm_out, coef_out);
+  HIP_TRY2(hipGetLastError());
+  return STGCN_OK;
+}
+
+int stgcn_seed_next(uint64_t *counter, uint64_t *token, void *stream) {
+  if (!counter) return fail(STGCN_E_INVALID, "seed_next: counter is null");
+  if (!token) return fail(STGCN_E_INVALID, "seed_next: token is null");
+  if (int rc = check_aligned({NP(counter), NP(token)}, 8)) return rc;
+  hipLaunchKernelGGL(k_seed_next, dim3(1), dim3(1), 0, (hipStream_t)stream, counter, token);
+  HIP_TRY2(hipGetLastError());
+  return STGCN_OK;
+}
+
 int stgcn_head_fwd(const stgcn_head_desc_t *d, const float *y, const float *W, const float *bias,
                    const int64_t *labels, float *pooled, float *logits, float *lossv, float *loss,
                    void *stream) {
@@ -565,7 +711,9 @@ int stgcn_head_fwd_u(const stgcn_head_desc_t *d, const float *U, const float *st
   return STGCN_OK;
 }
 
-int stgcn_features(void) { return STGCN_FEATURE_EVAL_CHAIN | STGCN_FEATURE_EVAL_HEAD; }
+int stgcn_features(void) {
+  return STGCN_FEATURE_EVAL_CHAIN | STGCN_FEATURE_EVAL_HEAD | STGCN_FEATURE_STEP_STATE;
+}
 
 // (classes of a metrics block: the head's own LDS limit at C = 1)
 static bool eval_classes_ok(int classes) {

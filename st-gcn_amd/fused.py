@@ -11,6 +11,7 @@ math is that of ``SpatialTemporalConv.forward`` (src/network/st_graphconv.py:
 import ctypes
 import weakref
 
+import numpy as np
 import torch
 
 from . import hip_lib
@@ -348,10 +349,92 @@ def _chain_publish(cc, prev_sums, dx, dx_coef=None):
 
 def _dropout_seed(drop, training):
     """Seed of this call's fused dropout, drawn from torch's default generator
-    (so torch.manual_seed reproduces it); 0 when inactive."""
+    (so torch.manual_seed reproduces it); 0 when inactive. A host seed is a
+    by-value kernel argument: a stream capture would freeze it and every replay
+    would apply the same mask, so drawing one during a capture raises."""
     if not (training and drop > 0):
         return 0
+    if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+        raise RuntimeError(
+            "fused dropout with a host seed inside a stream capture: every replay would "
+            "apply the same mask. Use STGCNStack(..., dropout_seed=\"device\") (or a block's "
+            "drop_counter = fused.DropoutCounter(device)) so the mask follows a device counter")
     return int(torch.randint(0, 2 ** 62, (1,)).item())
+
+
+_PHI = 0x9E3779B97F4A7C15
+_M64 = (1 << 64) - 1
+
+
+def _mix64(z):
+    """splitmix64's finaliser on a Python int (mod 2^64): csrc/internal.h mix64."""
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def dropout_mask(seed, shape, p, counter=None):
+    """The keep mask of the fused dropout as a bool numpy array of ``shape``
+    (stgcn_hip.h, stgcn_block_fwd_dseed): element e (flat index) is kept iff
+    hi32(mix64(s + e * PHI)) >= p * 2^32, with s = seed, or, given the step
+    token ``counter``, s = mix64(seed + counter * PHI). Kept elements are
+    scaled by 1 / (1 - p). Host code: no GPU, no library."""
+    s = int(seed) & _M64
+    if counter is not None:
+        s = _mix64((s + (int(counter) & _M64) * _PHI) & _M64)
+    e = np.arange(int(np.prod(shape)), dtype=np.uint64)
+    with np.errstate(over="ignore"):
+        z = np.uint64(s) + e * np.uint64(_PHI)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        z ^= z >> np.uint64(31)
+    thresh = min(int(float(p) * 2.0 ** 32), 2 ** 32 - 1)
+    return ((z >> np.uint64(32)) >= np.uint64(thresh)).reshape(shape)
+
+
+def draw_salt():
+    """A block's fixed dropout salt for device seeding, from torch's default
+    generator (so torch.manual_seed reproduces a run)."""
+    return int(torch.randint(0, 2 ** 62, (1,)).item())
+
+
+class DropoutCounter:
+    """The dropout step counter in device memory (an int64 tensor of one
+    element, read by the library as a 64-bit word). ``next()`` advances it on
+    the current stream and returns a fresh one-element token tensor holding the
+    new count (stgcn_seed_next); a forward hands the token to its blocks
+    (stgcn_block_fwd_dseed) and keeps it for its backward, so a later forward
+    -- gradient accumulation -- never changes the mask an earlier backward
+    regenerates. Nothing is read on the host: inside a captured step every
+    replay advances the counter and draws new masks. counter: an existing
+    tensor to use (a module's buffer) instead of a new one."""
+
+    def __init__(self, device="cuda", counter=None):
+        if counter is None:
+            counter = torch.zeros(1, device=device, dtype=torch.int64)
+        elif (counter.dtype != torch.int64 or not counter.is_cuda or counter.numel() != 1
+              or counter.data_ptr() % 8):
+            raise ValueError("DropoutCounter: counter must be a one-element int64 GPU tensor")
+        self.counter = counter
+
+    def next(self):
+        dev = self.counter.device
+        token = torch.empty(1, device=dev, dtype=torch.int64)
+        hip_lib.check(hip_lib.lib().stgcn_seed_next(
+            hip_lib.ptr(self.counter), hip_lib.ptr(token), hip_lib.stream_handle(dev)))
+        return token
+
+
+def _seed_args(drop, training, dseed):
+    """(seed, token) of a block call: dseed = (salt, token tensor) seeds the
+    dropout from device memory (the by-value seed is the block's fixed salt),
+    else a host seed is drawn and the token is None."""
+    if dseed is None or not (training and drop > 0):
+        return _dropout_seed(drop, training), None
+    salt, token = dseed
+    if token.dtype != torch.int64 or not token.is_cuda or token.numel() != 1:
+        raise RuntimeError("dropout token: expected a one-element int64 GPU tensor")
+    return int(salt), token
 
 
 def _per_row(dy):
@@ -396,7 +479,8 @@ class StgcnBlockFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, A, W, bW, Wt, bWt, g1, b1, g2, b2, rm1, rv1, rm2, rv2,
-                stride, pad, eps, momentum, training, cc=None, drop=0.0, gemm="fp32"):
+                stride, pad, eps, momentum, training, cc=None, drop=0.0, gemm="fp32",
+                dseed=None):
         lib = hip_lib.lib()
         # (the caller's input tensor: a hook / retain_grad() on it turns deferred dx off)
         ctx.xref = weakref.ref(x) if cc is not None else None
@@ -411,7 +495,7 @@ class StgcnBlockFn(torch.autograd.Function):
         names = ("x", "A", "W", "bW", "Wt", "bWt", "g1", "b1", "g2", "b2",
                  "rm1", "rv1", "rm2", "rv2")
         tensors = (x, A, W, bW, Wt, bWt, g1, b1, g2, b2, rm1, rv1, rm2, rv2)
-        seed = _dropout_seed(drop, training)
+        seed, token = _seed_args(drop, training, dseed)
         x, A, W, bW, Wt, bWt, g1, b1, g2, b2, rm1, rv1, rm2, rv2 = (
             t if xu and n == "x" else _f32c(t, n, inout=n[0] == "r")
             for t, n in zip(tensors, names))
@@ -442,8 +526,10 @@ class StgcnBlockFn(torch.autograd.Function):
             args.prev_U, args.prev_stats = hip_lib.ptr(cc.prev_U), hip_lib.ptr(cc.prev_stats)
             args.prev_g2, args.prev_b2 = hip_lib.ptr(pg2), hip_lib.ptr(pb2)
         ctx.x_lazy = xu
-        hip_lib.check(lib.stgcn_block_fwd(ctypes.byref(desc), ctypes.byref(args),
-                                          hip_lib.ptr(ws), nbytes, hip_lib.stream_handle(dev)))
+        hip_lib.check(lib.stgcn_block_fwd_dseed(ctypes.byref(desc), ctypes.byref(args),
+                                                hip_lib.ptr(token), hip_lib.ptr(ws), nbytes,
+                                                hip_lib.stream_handle(dev)))
+        ctx.token = token  # (this forward's own: the backward regenerates its mask)
         ctx.save_for_backward(x, Z, U, stats, A, W, bW, Wt, g1, b1, g2, b2, G)
         ctx.prep = prep
         if cc is not None:
@@ -487,18 +573,20 @@ class StgcnBlockFn(torch.autograd.Function):
             dx_coef=hip_lib.ptr(dx_coef),
             dx_deferred=ctypes.addressof(deferred) if dx_coef is not None else None,
             dy_coef=hip_lib.ptr(dy_coef), prep=hip_lib.ptr(ctx.prep), dy_nc=hip_lib.ptr(dy_nc))
-        rc = lib.stgcn_block_bwd(ctypes.byref(desc), ctypes.byref(args), hip_lib.ptr(ws), nbytes,
-                                 hip_lib.stream_handle(x.device))
+        tok = hip_lib.ptr(ctx.token)
+        rc = lib.stgcn_block_bwd_dseed(ctypes.byref(desc), ctypes.byref(args), tok,
+                                       hip_lib.ptr(ws), nbytes, hip_lib.stream_handle(x.device))
         if rc == hip_lib.E_UNSUPPORTED and dy_nc is not None:  # (needs the full dy)
             dy = _aligned16(dy_full.contiguous())
             args.dy, args.dy_nc = hip_lib.ptr(dy), None
-            rc = lib.stgcn_block_bwd(ctypes.byref(desc), ctypes.byref(args), hip_lib.ptr(ws),
-                                     nbytes, hip_lib.stream_handle(x.device))
+            rc = lib.stgcn_block_bwd_dseed(ctypes.byref(desc), ctypes.byref(args), tok,
+                                           hip_lib.ptr(ws), nbytes,
+                                           hip_lib.stream_handle(x.device))
         hip_lib.check(rc)
         _chain_publish(ctx.cc, psums, dx, dx_coef if deferred.value else None)
         dA, dW, dbW, dWt = grads
         return (dx, dA, dW, dbW, dWt, dbWt, dg1, db1, dg2, db2,
-                None, None, None, None, None, None, None, None, None, None, None, None)
+                None, None, None, None, None, None, None, None, None, None, None, None, None)
 
 
 class StgcnResBlockFn(torch.autograd.Function):
@@ -514,10 +602,11 @@ class StgcnResBlockFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, A, W, bW, Wt, bWt, g1, b1, g2, b2, Wr, br, rm1, rv1, rm2, rv2,
-                stride, pad, eps, momentum, training, cc=None, drop=0.0, gemm="fp32"):
+                stride, pad, eps, momentum, training, cc=None, drop=0.0, gemm="fp32",
+                dseed=None):
         lib = hip_lib.lib()
         x = x.contiguous()
-        seed = _dropout_seed(drop, training)
+        seed, token = _seed_args(drop, training, dseed)
         names = ("x", "A", "W", "bW", "Wt", "bWt", "g1", "b1", "g2", "b2",
                  "rm1", "rv1", "rm2", "rv2")
         x, A, W, bW, Wt, bWt, g1, b1, g2, b2, rm1, rv1, rm2, rv2 = (
@@ -544,8 +633,10 @@ class StgcnResBlockFn(torch.autograd.Function):
         args = _args(hip_lib.FwdArgs, [hip_lib.ptr(t) for t in (
             x, A, W, bW, Wt, bWt, g1, b1, g2, b2, rm1, rv1, rm2, rv2, y, Z, None, stats,
             Wr, br, Za, G, cc and cc.x_stats, cc and cc.y_stats)], drop, seed)
-        hip_lib.check(lib.stgcn_block_fwd(ctypes.byref(desc), ctypes.byref(args),
-                                          hip_lib.ptr(ws), nbytes, hip_lib.stream_handle(dev)))
+        hip_lib.check(lib.stgcn_block_fwd_dseed(ctypes.byref(desc), ctypes.byref(args),
+                                                hip_lib.ptr(token), hip_lib.ptr(ws), nbytes,
+                                                hip_lib.stream_handle(dev)))
+        ctx.token = token
         ctx.save_for_backward(x, Z, Za, y, stats, A, W, bW, Wt, g1, b1, g2, b2, Wr, G)
         ctx.cfg = (stride, pad, eps, momentum, training)
         ctx.gemm = gemm
@@ -580,11 +671,12 @@ class StgcnResBlockFn(torch.autograd.Function):
             dA, dW, dbW, dWt, dbWt, dg1, db1, dg2, db2,
             Wr, Za, y, dWr, dbr, G, None, pg2, pb2, psums)], *ctx.drop,
             prev_U=hip_lib.ptr(pU), prev_stats=hip_lib.ptr(pst))
-        hip_lib.check(lib.stgcn_block_bwd(ctypes.byref(desc), ctypes.byref(args),
-                                          hip_lib.ptr(ws), nbytes, hip_lib.stream_handle(dev)))
+        hip_lib.check(lib.stgcn_block_bwd_dseed(ctypes.byref(desc), ctypes.byref(args),
+                                                hip_lib.ptr(ctx.token), hip_lib.ptr(ws), nbytes,
+                                                hip_lib.stream_handle(dev)))
         _chain_publish(ctx.cc, psums, dx)
         return (dx, dA, dW, dbW, dWt, dbWt, dg1, db1, dg2, db2, dWr, dbr,
-                None, None, None, None, None, None, None, None, None, None, None, None)
+                None, None, None, None, None, None, None, None, None, None, None, None, None)
 
 
 class SpatialConvFn(torch.autograd.Function):

@@ -35,6 +35,7 @@ PLAN_X_FROM_U = 512  # ABI 8: the input as ReLU(BN2(U)) of the previous block
 PLAN_X_FROM_U_EVAL = 1024  # ... in the eval forward (stgcn_features: FEATURE_EVAL_CHAIN)
 # stgcn_features bits: additions within ABI 11
 FEATURE_EVAL_CHAIN, FEATURE_EVAL_HEAD = 1, 2
+FEATURE_STEP_STATE = 4  # per-step values from device memory (dropout token, lr, clip)
 METRICS_WORDS = 8  # 8-byte words of a metrics block before its confusion matrix
 # ABI 7: a y_stats / x_stats block: 5 * C doubles, then STATS_AMAX_WORDS uint32 (max |y|)
 STATS_AMAX_WORDS = 2048
@@ -116,7 +117,9 @@ EXPORTED = ("stgcn_abi_version", "stgcn_last_error", "stgcn_check_desc",
             "stgcn_block_plan", "stgcn_fold_prep_bytes", "stgcn_fold_prep", "stgcn_head_fwd_u",
             "stgcn_head_bwd_nc", "stgcn_adam_step_dev", "stgcn_features",
             "stgcn_eval_metrics_bytes", "stgcn_eval_metrics_reset", "stgcn_head_eval",
-            "stgcn_head_eval_u")
+            "stgcn_head_eval_u", "stgcn_block_fwd_dseed", "stgcn_block_bwd_dseed",
+            "stgcn_seed_next", "stgcn_adam_step_dev2", "stgcn_grad_norm_bytes",
+            "stgcn_grad_norm")
 
 _LIB = None
 
@@ -142,6 +145,14 @@ def load_library(path=LIB_PATH):
     lib.stgcn_block_bwd.argtypes = [ctypes.POINTER(Desc), ctypes.POINTER(BwdArgs), _vp,
                                     ctypes.c_size_t, _vp]
     lib.stgcn_block_bwd.restype = ctypes.c_int
+    lib.stgcn_block_fwd_dseed.argtypes = [ctypes.POINTER(Desc), ctypes.POINTER(FwdArgs), _vp, _vp,
+                                          ctypes.c_size_t, _vp]
+    lib.stgcn_block_fwd_dseed.restype = ctypes.c_int
+    lib.stgcn_block_bwd_dseed.argtypes = [ctypes.POINTER(Desc), ctypes.POINTER(BwdArgs), _vp, _vp,
+                                          ctypes.c_size_t, _vp]
+    lib.stgcn_block_bwd_dseed.restype = ctypes.c_int
+    lib.stgcn_seed_next.argtypes = [_vp, _vp, _vp]
+    lib.stgcn_seed_next.restype = ctypes.c_int
     lib.stgcn_time_kernel_bytes.argtypes = [ctypes.POINTER(Desc), ctypes.c_int]
     lib.stgcn_time_kernel_bytes.restype = ctypes.c_size_t
     lib.stgcn_time_kernel.argtypes = [ctypes.POINTER(Desc), ctypes.c_int, _vp, ctypes.c_size_t,
@@ -176,6 +187,14 @@ def load_library(path=LIB_PATH):
     lib.stgcn_adam_step_dev.argtypes = [_vp, ctypes.c_int, ctypes.c_int64] + \
         [ctypes.c_double] * 5 + [_vp, _vp]
     lib.stgcn_adam_step_dev.restype = ctypes.c_int
+    lib.stgcn_adam_step_dev2.argtypes = [_vp, ctypes.c_int, ctypes.c_int64, _vp, _vp] + \
+        [ctypes.c_double] * 4 + [_vp, _vp]
+    lib.stgcn_adam_step_dev2.restype = ctypes.c_int
+    lib.stgcn_grad_norm_bytes.argtypes = [ctypes.c_int64]
+    lib.stgcn_grad_norm_bytes.restype = ctypes.c_size_t
+    lib.stgcn_grad_norm.argtypes = [_vp, ctypes.c_int, ctypes.c_int64, ctypes.c_double,
+                                    _vp, _vp, _vp, _vp]
+    lib.stgcn_grad_norm.restype = ctypes.c_int
     lib.stgcn_spatial_workspace_bytes.argtypes = [ctypes.POINTER(SpatialDesc), ctypes.c_int]
     lib.stgcn_spatial_workspace_bytes.restype = ctypes.c_size_t
     lib.stgcn_spatial_fwd.argtypes = [ctypes.POINTER(SpatialDesc)] + [_vp] * 6 + \

@@ -8,8 +8,8 @@ import torch
 import torch.nn as nn
 
 from .graph import Strategy, get_normalized_adjacency_matrices
-from .fused import (FoldPrep, eval_forward, eval_links, head_link_ok, lazy_links,
-                    stack_descs)
+from .fused import (DropoutCounter, FoldPrep, draw_salt, eval_forward, eval_links,
+                    head_link_ok, lazy_links, stack_descs)
 from .network import SpatialTemporalConv, StackChain
 from .train_ops import EvalMetrics, StgcnHeadFn, head_eval
 
@@ -33,12 +33,26 @@ class STGCNStack(nn.Module):
     turns the deferral off for that link (the true gradient is formed and seen);
     ``torch.autograd.grad(loss, block_output)`` cannot be detected from inside
     the block and is not supported in a chained training step (run the blocks
-    unchained, e.g. one by one, for that)."""
+    unchained, e.g. one by one, for that).
+
+    dropout_seed: "host" (default) draws each block call's dropout seed from
+    torch's default generator on the host; a stream capture refuses that (every
+    replay would repeat the mask). "device": the masks follow a counter in
+    device memory (``drop_counter``, a non-persistent int64 buffer, so the
+    state_dict keys stay the reference's): every training forward takes one
+    token from it (fused.DropoutCounter) and each block combines the token with
+    its own fixed salt, drawn once here from torch's default generator (after
+    the parameters' initialisation, so torch.manual_seed reproduces both). The
+    step can then be captured (train_ops.GraphedStep) and every replay draws
+    new masks."""
 
     def __init__(self, C_in, nr_classes, A, gamma=9, dropout_rate=0, residual=False,
                  gemm_dtype=torch.float32, f32_gemm="mfma", use_edge_importance=False,
-                 max_mask_jitter=0.001):
+                 max_mask_jitter=0.001, dropout_seed="host"):
         super().__init__()
+        if dropout_seed not in ("host", "device"):
+            raise ValueError("dropout_seed must be 'host' or 'device'")
+        self.dropout_seed = dropout_seed
         pad = (gamma - 1) // 2
         self.K, self.V = A.shape[0], A.shape[1]
         self.nr_classes = nr_classes
@@ -57,6 +71,11 @@ class STGCNStack(nn.Module):
             c = co
         self.conv = nn.Sequential(*blocks).float()
         self.fc_layer = nn.Linear(256, nr_classes).float()
+        if dropout_seed == "device":
+            self.register_buffer("drop_counter", torch.zeros(1, dtype=torch.int64),
+                                 persistent=False)
+            for blk in self.conv:
+                blk.drop_salt = draw_salt()
 
     def _chain(self, x, head=False):
         """The StackChain of a training forward, with the stack's folded blocks'
@@ -66,6 +85,9 @@ class STGCNStack(nn.Module):
         if not self.training:
             return None
         chain = StackChain(defer_counts=True)
+        if (getattr(self, "dropout_seed", "host") == "device" and x.is_cuda
+                and any(b.dropout is not None and b.dropout.p > 0 for b in self.conv)):
+            chain.drop_token = DropoutCounter(counter=self.drop_counter).next()
         if x.is_cuda:
             if getattr(self, "_fold_prep", None) is None:
                 self._fold_prep = FoldPrep()

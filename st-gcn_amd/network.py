@@ -13,7 +13,7 @@ import torch
 import torch.nn as nn
 
 from . import hip_lib
-from .fused import ChainCtx, Link, SpatialConvFn, StgcnBlockFn, StgcnResBlockFn
+from .fused import ChainCtx, Link, SpatialConvFn, StgcnBlockFn, StgcnResBlockFn, draw_salt
 
 
 class StackChain:
@@ -31,6 +31,9 @@ class StackChain:
         num_batches_tracked increments itself with ``flush_counts``."""
         self.defer_counts = defer_counts
         self.counters = []
+        # the forward's dropout token (model.STGCNStack(dropout_seed="device")): one
+        # fused.DropoutCounter.next() per forward, shared by its dropout blocks
+        self.drop_token = None
         self.reset()
 
     def reset(self):
@@ -106,6 +109,13 @@ class SpatialTemporalConv(nn.Module):
     st_graphconv.py:60-82), training and eval mode, with dropout (p > 0,
     training) fused into the block's output pass (counter-based mask,
     regenerated in backward; a different random stream from torch's).
+
+    ``drop_counter`` (not in the reference; default None): a
+    ``fused.DropoutCounter``. With one, the mask is seeded from device memory --
+    the block's fixed salt (``drop_salt``, drawn once from torch's default
+    generator) combined with a token the counter hands to each forward -- so a
+    forward captured in a HIP graph draws a new mask on every replay. Without
+    one the seed is drawn on the host per call, which a capture refuses.
     """
 
     def __init__(self, C_in, C_out, A, gamma, temporal_stride, temporal_padding,
@@ -152,6 +162,22 @@ class SpatialTemporalConv(nn.Module):
         self.gamma = gamma
         self.stride = temporal_stride
         self.pad = temporal_padding
+        self.drop_counter = None
+        self.drop_salt = None
+
+    def _device_seed(self, chain, drop):
+        """(salt, token) when this forward's dropout is seeded from device memory
+        (the stack's token of this forward, or the block's own drop_counter)."""
+        if not drop > 0:
+            return None
+        token = chain.drop_token if chain is not None else None
+        if token is None and getattr(self, "drop_counter", None) is not None:
+            token = self.drop_counter.next()
+        if token is None:
+            return None
+        if getattr(self, "drop_salt", None) is None:
+            self.drop_salt = draw_salt()
+        return (self.drop_salt, token)
 
     def gemm_mode(self):
         """The channel-GEMM arithmetic of this block (fused._gemm_flags mode)."""
@@ -175,6 +201,7 @@ class SpatialTemporalConv(nn.Module):
         x = f_in.float()
         drop = self.dropout.p if (self.dropout is not None and training) else 0.0
         gemm = self.gemm_mode()
+        dseed = self._device_seed(chain, drop)
         cc = None
         lazy = chain.next_lazy() if chain is not None else False
         if chain is not None and chain.y_lazy and not (
@@ -216,13 +243,13 @@ class SpatialTemporalConv(nn.Module):
                 proj.weight if proj is not None else None,
                 proj.bias if proj is not None else None,
                 bn1.running_mean, bn1.running_var, bn2.running_mean, bn2.running_var,
-                self.stride, self.pad, bn1.eps, bn1.momentum, training, cc, drop, gemm)
+                self.stride, self.pad, bn1.eps, bn1.momentum, training, cc, drop, gemm, dseed)
         else:
             y = StgcnBlockFn.apply(
                 x, sc.A, sc.W.weight, sc.W.bias, self.temporalConv.weight,
                 self.temporalConv.bias, bn1.weight, bn1.bias, bn2.weight, bn2.bias,
                 bn1.running_mean, bn1.running_var, bn2.running_mean, bn2.running_var,
-                self.stride, self.pad, bn1.eps, bn1.momentum, training, cc, drop, gemm)
+                self.stride, self.pad, bn1.eps, bn1.momentum, training, cc, drop, gemm, dseed)
         if chain is not None:
             if cc is None:
                 chain.reset()

@@ -222,14 +222,40 @@ class FusedAdam(torch.optim.Optimizer):
     graph (``GraphedStep``). A table built during a capture (the captured
     backward allocates new gradients) is written into a pinned buffer set aside
     by the last eager build and kept alive with the table: every replay's copy
-    re-reads it."""
+    re-reads it.
+
+    lr as a tensor (capturable=True only): a 0-dim float32 tensor on the
+    parameters' device is read by the kernel when it runs (stgcn_adam_step_dev2),
+    so a scheduler that writes it with ``fill_`` between replays (torch's
+    lr_scheduler does for a tensor lr) takes effect without a re-capture. Any
+    other tensor raises; a float lr takes the by-value call as before.
+
+    max_grad_norm (capturable=True only): the 2-norm of all gradients of all
+    groups is formed on the device (stgcn_grad_norm: fixed-order fp64 sums, no
+    atomics, the same bits every run) and the step uses g * clip_coef with
+    clip_coef = min(1, max_grad_norm / (norm + 1e-6)), the coefficient of
+    ``torch.nn.utils.clip_grad_norm_``, applied before the weight-decay term as
+    when clip_grad_norm_ runs before step(). ``opt.grad_norm`` and
+    ``opt.clip_coef`` are the device tensors of the last step. Unlike
+    clip_grad_norm_, ``p.grad`` itself is NOT rescaled: code that reads the
+    gradients after the step sees the unclipped ones. Under data parallelism the
+    step runs after the all-reduce, so the norm is the global one."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0,
-                 amsgrad=False, capturable=False):
+                 amsgrad=False, capturable=False, max_grad_norm=None):
         if amsgrad:
             raise NotImplementedError("FusedAdam: amsgrad")
+        if max_grad_norm is not None:
+            if not capturable:
+                raise ValueError("FusedAdam: max_grad_norm needs capturable=True")
+            if not float(max_grad_norm) > 0:
+                raise ValueError("FusedAdam: max_grad_norm must be positive")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self.capturable = capturable
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.grad_norm = self.clip_coef = None  # device tensors (max_grad_norm)
+        self._norm_partials = None
+        self._lr_dev = {}  # group index -> (value, device float) of a float lr (clipping)
         self._tables = {}  # group index -> (key, device table, chunks, ntensors, host table)
         self._spare = {}   # group index -> unused pinned table buffer (capturable)
         self._captured = []  # pinned tables a captured step's copies read
@@ -241,6 +267,7 @@ class FusedAdam(torch.optim.Optimizer):
             with torch.enable_grad():
                 loss = closure()
         lib = hip_lib.lib()
+        coef = self._clip() if self.max_grad_norm is not None else None
         for gi, group in enumerate(self.param_groups):
             plist = [p for p in group["params"] if p.grad is not None]
             if not plist:
@@ -248,6 +275,13 @@ class FusedAdam(torch.optim.Optimizer):
             for p in plist:
                 _check_f32(p, "param")
                 _check_f32(p.grad, "grad")
+            lr = group["lr"]
+            if torch.is_tensor(lr):
+                if not (self.capturable and lr.dim() == 0 and lr.dtype == torch.float32
+                        and lr.device == plist[0].device):
+                    raise RuntimeError(
+                        "FusedAdam: a tensor lr must be a 0-dim float32 tensor on the "
+                        "parameters' device, with capturable=True")
             if self.capturable:
                 dstep = self._device_step(plist)
             else:
@@ -262,39 +296,17 @@ class FusedAdam(torch.optim.Optimizer):
                 if len(steps) != 1:
                     raise RuntimeError("FusedAdam: parameters of a group at different steps")
                 step = steps.pop()
-            tabs = [hip_lib.AdamTensor(p.data_ptr(), p.grad.data_ptr(),
-                                       self.state[p]["exp_avg"].data_ptr(),
-                                       self.state[p]["exp_avg_sq"].data_ptr(), p.numel())
-                    for p in plist]
-            key = tuple((t.param, t.grad, t.exp_avg, t.exp_avg_sq, t.numel) for t in tabs)
             dev = plist[0].device
-            cached = self._tables.get(gi)
-            if cached is None or cached[0] != key:
-                n = len(tabs)
-                nbytes = lib.stgcn_adam_table_bytes(n)
-                if torch.cuda.is_current_stream_capturing():
-                    # (no pinned allocation inside a capture: the spare buffer
-                    # the last eager build left, never yet read by a copy)
-                    host = self._spare.pop(gi, None)
-                    if host is None or host.numel() < nbytes:
-                        raise RuntimeError("FusedAdam: capture a step only after an eager "
-                                           "step of the same parameters (GraphedStep warm-up)")
-                    self._captured.append(host)  # (read by every replay: never freed)
-                else:
-                    host = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
-                    if self.capturable:
-                        self._spare[gi] = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
-                chunks = ctypes.c_int64(0)
-                arr = (hip_lib.AdamTensor * n)(*tabs)
-                hip_lib.check(lib.stgcn_adam_build_table(arr, n, ctypes.c_void_p(host.data_ptr()),
-                                                         nbytes, ctypes.byref(chunks)))
-                dev_table = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-                dev_table.copy_(host, non_blocking=True)
-                cached = (key, dev_table, chunks.value, n, host)
-                self._tables[gi] = cached
-            _, dev_table, nchunks, n, _ = cached
+            _, dev_table, nchunks, n, _ = self._table(gi, plist)
             b1, b2 = group["betas"]
-            if self.capturable:
+            if self.capturable and (torch.is_tensor(lr) or coef is not None):
+                if not torch.is_tensor(lr):  # (a float lr next to clipping)
+                    lr = self._lr_tensor(gi, lr, dev)
+                hip_lib.check(lib.stgcn_adam_step_dev2(
+                    hip_lib.ptr(dev_table), n, nchunks, hip_lib.ptr(lr), hip_lib.ptr(coef),
+                    b1, b2, group["eps"], group["weight_decay"], hip_lib.ptr(dstep),
+                    hip_lib.stream_handle(dev)))
+            elif self.capturable:
                 hip_lib.check(lib.stgcn_adam_step_dev(
                     hip_lib.ptr(dev_table), n, nchunks, group["lr"], b1, b2,
                     group["eps"], group["weight_decay"], hip_lib.ptr(dstep),
@@ -304,6 +316,84 @@ class FusedAdam(torch.optim.Optimizer):
                     hip_lib.ptr(dev_table), n, nchunks, group["lr"], b1, b2,
                     group["eps"], group["weight_decay"], step, hip_lib.stream_handle(dev)))
         return loss
+
+    def _table(self, gi, plist):
+        """(key, device table, chunks, ntensors, host table) of the tensors of
+        ``plist``, cached under ``gi`` and rebuilt when a pointer changed."""
+        lib = hip_lib.lib()
+        tabs = [hip_lib.AdamTensor(p.data_ptr(), p.grad.data_ptr(),
+                                   self.state[p]["exp_avg"].data_ptr(),
+                                   self.state[p]["exp_avg_sq"].data_ptr(), p.numel())
+                for p in plist]
+        key = tuple((t.param, t.grad, t.exp_avg, t.exp_avg_sq, t.numel) for t in tabs)
+        dev = plist[0].device
+        cached = self._tables.get(gi)
+        if cached is None or cached[0] != key:
+            n = len(tabs)
+            nbytes = lib.stgcn_adam_table_bytes(n)
+            if torch.cuda.is_current_stream_capturing():
+                # (no pinned allocation inside a capture: the spare buffer
+                # the last eager build left, never yet read by a copy)
+                host = self._spare.pop(gi, None)
+                if host is None or host.numel() < nbytes:
+                    raise RuntimeError("FusedAdam: capture a step only after an eager "
+                                       "step of the same parameters (GraphedStep warm-up)")
+                self._captured.append(host)  # (read by every replay: never freed)
+            else:
+                host = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+                if self.capturable:
+                    self._spare[gi] = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+            chunks = ctypes.c_int64(0)
+            arr = (hip_lib.AdamTensor * n)(*tabs)
+            hip_lib.check(lib.stgcn_adam_build_table(arr, n, ctypes.c_void_p(host.data_ptr()),
+                                                     nbytes, ctypes.byref(chunks)))
+            dev_table = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            dev_table.copy_(host, non_blocking=True)
+            cached = (key, dev_table, chunks.value, n, host)
+            self._tables[gi] = cached
+        return cached
+
+    def _lr_tensor(self, gi, lr, dev):
+        """A float lr as the device word stgcn_adam_step_dev2 reads (the clipped
+        step with a float lr; the value rounded to float32, as a tensor lr is):
+        rewritten when the value changes; inside a capture the write is part of
+        the graph, so a captured step keeps its capture's value, like the
+        by-value call."""
+        held = self._lr_dev.get(gi)
+        if held is None or held[0] != float(lr):
+            held = (float(lr), torch.full((), float(lr), device=dev, dtype=torch.float32))
+            self._lr_dev[gi] = held
+        return held[1]
+
+    def _clip(self):
+        """The global gradient norm and clip coefficient of this step on the
+        device (one table over every group's tensors); returns clip_coef."""
+        lib = hip_lib.lib()
+        plist = [p for g in self.param_groups for p in g["params"] if p.grad is not None]
+        if not plist:
+            return None
+        for p in plist:
+            _check_f32(p, "param")
+            _check_f32(p.grad, "grad")
+        for g in self.param_groups:  # (the table carries the state pointers: create them)
+            gp = [p for p in g["params"] if p.grad is not None]
+            if gp:
+                self._device_step(gp)
+        dev = plist[0].device
+        _, dev_table, nchunks, n, _ = self._table("norm", plist)
+        if self.grad_norm is None:
+            self.grad_norm = torch.zeros((), device=dev, dtype=torch.float32)
+            self.clip_coef = torch.ones((), device=dev, dtype=torch.float32)
+        need = lib.stgcn_grad_norm_bytes(nchunks) // 8
+        if self._norm_partials is None or self._norm_partials.numel() < need:
+            if torch.cuda.is_current_stream_capturing() and self._norm_partials is not None:
+                raise RuntimeError("FusedAdam: the parameter set grew inside a capture")
+            self._norm_partials = torch.empty(need, device=dev, dtype=torch.float64)
+        hip_lib.check(lib.stgcn_grad_norm(
+            hip_lib.ptr(dev_table), n, nchunks, self.max_grad_norm,
+            hip_lib.ptr(self._norm_partials), hip_lib.ptr(self.grad_norm),
+            hip_lib.ptr(self.clip_coef), hip_lib.stream_handle(dev)))
+        return self.clip_coef
 
     def _device_step(self, plist):
         """The group's device step count (float32, shape ()): created with the
@@ -334,9 +424,11 @@ class GraphedStep:
     over the caller's stream work: every libstgcn_hip launch goes to the capture
     stream, allocations come from the graph's private pool, so replays reuse the
     same buffers). ``step_fn()`` must be replay-safe: static inputs (copy new
-    data into them before ``__call__``), no host reads of device values, no
-    dropout (its seed is drawn on the host), optimizer ``FusedAdam(capturable=
-    True)``. ``warmup`` eager calls run first on a side stream (the torch
+    data into them before ``__call__``), no host reads of device values,
+    optimizer ``FusedAdam(capturable=True)``. Per-step values come from device
+    memory: dropout needs ``STGCNStack(dropout_seed="device")`` (a host seed
+    raises at capture), a learning-rate schedule a tensor ``lr``, clipping
+    ``FusedAdam(max_grad_norm=...)``. ``warmup`` eager calls run first on a side stream (the torch
     recipe: lazy allocations and table builds happen outside the capture).
     ``__call__`` replays and returns the tensors the captured call returned
     (their storage is rewritten by every replay)."""
