@@ -55,6 +55,9 @@
  *       STGCN_FEATURE_STEP_STATE: seed_dev (stgcn_block_fwd_dseed / _bwd_dseed)
  *         and stgcn_seed_next's counter / token 8 (64-bit words); lr_dev,
  *         grad_coef, norm_out, coef_out 4; stgcn_grad_norm's partials 8.
+ *       STGCN_FEATURE_INPUT_STAGE (stgcn_input_stage): x 16 bytes, like a block
+ *         tensor; src its element's own 4 (fp32) or 8 (fp64) bytes; the clip
+ *         table 8; status 4.
  *     A caller with a misaligned read-only input for a 16-byte argument passes an
  *     aligned copy (the Python binding does); torch.empty results are aligned.
  *   - A is (K,V,V), W is (K*C_out, C_in) (the reference's 1x1 Conv2d weight),
@@ -293,6 +296,8 @@ const char *stgcn_last_error(void);
 #define STGCN_FEATURE_STEP_STATE 4 /* per-step values read from device memory: the _dseed
                                     * block calls, stgcn_seed_next, stgcn_adam_step_dev2,
                                     * stgcn_grad_norm                                     */
+#define STGCN_FEATURE_INPUT_STAGE 8 /* stgcn_input_check / stgcn_input_stage: ragged clips
+                                    * to the NCTV fp32 input on the device              */
 int stgcn_features(void);
 
 /* Validate a descriptor without touching the GPU (0 = supported). */
@@ -557,6 +562,48 @@ int stgcn_adam_step_dev2(const void *dev_table, int ntensors, int64_t total_chun
 size_t stgcn_grad_norm_bytes(int64_t total_chunks);
 int stgcn_grad_norm(const void *dev_table, int ntensors, int64_t total_chunks, double max_norm,
                     double *partials, float *norm_out, float *coef_out, void *stream);
+
+/* ---------------------------------------------------------------------------
+ * STGCN_FEATURE_INPUT_STAGE: the host input pipeline of the reference (loop
+ * padding src/data/util.py:12-47, augmentation src/data/augmentation.py:8-69
+ * drawn per clip as KTHDataset.__getitem__ does, datasets.py:154, the fp32
+ * cast and the NTVC -> NCTV permute of lightning_model.py:101) as one launch.
+ *
+ * src holds src_frames frames back to back, each V * C_src elements, joint
+ * major and channel fastest (the .npy layout (T, V, C_src)), fp32 or fp64.
+ * clips is a DEVICE table of N entries, read when the kernel runs (a captured
+ * launch sees the table's contents at each replay). For every (n, t, v),
+ *   frame = clips[n].first_frame + (t mod clips[n].frames)
+ * (np.pad "wrap"; a clip of T_out frames or more gives its first T_out),
+ *   x[n, j, t, v] = src[frame, v, 0] * m[0][j] + src[frame, v, 1] * m[1][j]
+ * for j = 0, 1 when flags bit 0 is set: two products and a sum in fp64 whatever
+ * the source type (no fused multiply-add), rounded once to fp32; m is the upper
+ * left 2x2 of the reference's 3x3 matrix (its third homogeneous coordinate is
+ * 0: translations do not move points). Without the bit channels 0 and 1 are
+ * cast like channels 2 .. C - 1: bit-exact, non-finite values included.
+ * An entry with frames < 1, first_frame < 0 or first_frame + frames >
+ * src_frames is invalid: its clip is written as zeros, status[n] = 1, and src
+ * is not read for it. status[n] = 0 otherwise; every launch writes all N words
+ * with plain stores (no atomics, nothing to reset between replays).
+ * Alignment: x 16 bytes, src its element's 4 or 8, clips 8, status 4. One
+ * launch on the caller's stream; nothing is allocated. */
+typedef struct stgcn_input_desc {
+  int32_t N, C, T_out, V; /* x (N, C, T_out, V) fp32                            */
+  int32_t C_src;          /* source channels per joint, C <= C_src <= 4, C >= 2 */
+  int32_t src_f64;        /* 0: fp32 source, 1: fp64                            */
+  int64_t src_frames;     /* capacity of src in frames                          */
+} stgcn_input_desc_t;
+typedef struct stgcn_clip { /* 48 bytes, device memory, N of them               */
+  int64_t first_frame;
+  int32_t frames;
+  int32_t flags;            /* bit 0: apply m                                   */
+  double m[4];              /* row-major 2x2, out_j = x m[0][j] + y m[1][j]     */
+} stgcn_clip_t;
+/* Validates a descriptor on the host (0 = supported; T_out * V and the launch
+ * grid must fit 31 bits). */
+int stgcn_input_check(const stgcn_input_desc_t *d);
+int stgcn_input_stage(const stgcn_input_desc_t *d, const void *src, const stgcn_clip_t *clips,
+                      float *x, int32_t *status, void *stream);
 
 #ifdef __cplusplus
 }

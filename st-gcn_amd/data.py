@@ -20,11 +20,22 @@ and what the reference leaves to Lightning: ``DeviceLoader`` turns collated
 consume (the permute of lightning_model.py:101, done on the GPU), staging
 through pinned host memory with the copy of batch i+1 in flight on a side
 stream while batch i trains. Variable T is fine: the HIP blocks take any T.
+
+Beside it, the same pipeline with the per-element work on the GPU
+(``pack_clips`` / ``clip_transforms`` / ``stage_clips`` /
+``RaggedDeviceLoader``): the host copies each ragged clip once into pinned
+memory, one HIP kernel (csrc/input_stage.hip) loop-pads, applies a transform
+drawn PER CLIP as the reference's dataset does (datasets.py:154), casts and
+transposes to NCTV, into a tensor the caller may own (a GraphedStep's input).
 """
+import ctypes
 import os
+import random
 
 import numpy as np
 import torch
+
+from . import hip_lib
 
 
 def pad_array_with_loops(x, target_len):
@@ -172,3 +183,259 @@ class DeviceLoader:
             xd.record_stream(cur)
             yd.record_stream(cur)
             yield xd.permute(0, 3, 1, 2).contiguous(), yd
+
+
+# ---------------------------------------------------------------------------
+# The input stage on the device (stgcn_input_stage, hip_lib.FEATURE_INPUT_STAGE):
+# the host only copies each clip's frames into pinned memory; the loop padding,
+# the per-clip augmentation, the fp32 cast and the transpose to NCTV are one
+# kernel (csrc/input_stage.hip).
+# ---------------------------------------------------------------------------
+
+# stgcn_clip_t (include/stgcn_hip.h), 48 bytes
+CLIP_DTYPE = np.dtype([("first_frame", "<i8"), ("frames", "<i4"), ("flags", "<i4"),
+                       ("m", "<f8", (4,))])
+assert CLIP_DTYPE.itemsize == ctypes.sizeof(hip_lib.Clip) == 48
+
+
+def clip_transforms(n, augment=True, rng=np.random, coin=random):
+    """(n, 3, 3) float64: the transform of each of n clips as the reference's
+    dataset draws it per item (KTHDataset.__getitem__, datasets.py:154): a coin
+    ``coin.randint(0, 1)``, and on 1 one ``augmentation_matrix(rng)``; the
+    identity on 0. Clip by clip, so ``coin`` and ``rng`` are consumed in the
+    reference's order. augment=False: identities, nothing drawn."""
+    out = np.tile(np.eye(3), (n, 1, 1))
+    if augment:
+        for i in range(n):
+            if coin.randint(0, 1):
+                out[i] = augmentation_matrix(rng)
+    return out
+
+
+def _np_dtype(dtype):
+    if isinstance(dtype, torch.dtype):
+        dtype = {torch.float32: np.float32, torch.float64: np.float64}.get(dtype, dtype)
+    dtype = np.dtype(dtype)
+    if dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise ValueError(f"pack_clips: the source is float32 or float64, not {dtype}")
+    return dtype
+
+
+def pack_clips(items, T_out, C_src, dtype, out=None, transforms=None):
+    """items: [(clip (T_i, V, C_src) or (1, T_i, V, C_src), label), ...] ->
+    (staging (frames, V, C_src) of ``dtype``, table (N,) CLIP_DTYPE, labels (N,)
+    int64). The first min(T_i, T_out) frames of every clip lie back to back in
+    item order (the kernel repeats a short clip from its start, so nothing is
+    padded here); table[i] says where clip i lies. transforms: (N, 3, 3) or
+    (N, 2, 2) matrices (``clip_transforms``); an identity, or None, gives
+    flags = 0 (the kernel's plain cast). out: a float array or CPU tensor of
+    ``dtype`` to pack into (pinned memory, for an asynchronous copy) with room
+    for the frames: N * T_out frames always suffice. Without it a new array."""
+    dtype = _np_dtype(dtype)
+    clips = []
+    for x, _ in items:
+        x = np.asarray(x)
+        if x.ndim == 4 and x.shape[0] == 1:
+            x = x[0]
+        if x.ndim != 3 or x.shape[2] != C_src or x.shape[0] < 1:
+            raise ValueError(f"pack_clips: a clip is (T >= 1, V, {C_src}), got {x.shape}")
+        clips.append(x)
+    N = len(clips)
+    if N == 0 or T_out < 1:
+        raise ValueError("pack_clips: needs at least one clip and T_out >= 1")
+    V = clips[0].shape[1]
+    if any(c.shape[1] != V for c in clips):
+        raise ValueError("pack_clips: the clips differ in their joint count")
+    frames = [min(c.shape[0], T_out) for c in clips]
+    total = sum(frames)
+    if out is None:
+        buf = np.empty((total, V, C_src), dtype=dtype)
+    else:
+        flat = out.numpy() if isinstance(out, torch.Tensor) else out
+        if flat.dtype != dtype or not flat.flags["C_CONTIGUOUS"]:
+            raise ValueError(f"pack_clips: out must be a contiguous {dtype} array")
+        flat = flat.reshape(-1)
+        if flat.size < total * V * C_src:
+            raise ValueError(f"pack_clips: out holds {flat.size} elements, the batch needs "
+                             f"{total * V * C_src}")
+        buf = flat[:total * V * C_src].reshape(total, V, C_src)
+    table = np.zeros(N, dtype=CLIP_DTYPE)
+    table["m"] = (1.0, 0.0, 0.0, 1.0)
+    first = 0
+    for i, (c, f) in enumerate(zip(clips, frames)):
+        buf[first:first + f] = c[:f]
+        table["first_frame"][i], table["frames"][i] = first, f
+        first += f
+    if transforms is not None:
+        transforms = np.asarray(transforms, dtype=np.float64)
+        if transforms.shape not in ((N, 3, 3), (N, 2, 2)):
+            raise ValueError(f"pack_clips: transforms is (N, 3, 3) or (N, 2, 2), "
+                             f"got {transforms.shape}")
+        eye = np.eye(transforms.shape[1])
+        for i, T in enumerate(transforms):
+            if not np.array_equal(T, eye):
+                table["flags"][i] = hip_lib.CLIP_APPLY
+                table["m"][i] = T[:2, :2].reshape(4)
+    labels = np.concatenate([np.asarray(y).reshape(-1) for _, y in items]).astype(np.int64)
+    return buf, table, labels
+
+
+def stage_clips(src, table, x, status):
+    """One stgcn_input_stage launch on the current stream: src (frames, V,
+    C_src) fp32 / fp64 on the device (its first dimension is the capacity the
+    kernel checks the table against), table the device copy of a CLIP_DTYPE
+    table (any dtype, N * 48 bytes), x (N, C, T_out, V) fp32 written in full,
+    status (N,) int32 written in full: 1 where the clip's entry was invalid
+    (that clip is zeros). The table is read when the kernel runs: inside a
+    captured graph, rewrite src and the table between replays. Returns x."""
+    if x.dtype != torch.float32 or x.dim() != 4 or not x.is_contiguous():
+        raise ValueError("stage_clips: x is a contiguous (N, C, T_out, V) float32 tensor")
+    N, C, T_out, V = x.shape
+    if src.dtype not in (torch.float32, torch.float64) or src.dim() != 3 or \
+            not src.is_contiguous() or src.shape[1] != V:
+        raise ValueError(f"stage_clips: src is a contiguous (frames, {V}, C_src) float32 or "
+                         f"float64 tensor, got {tuple(src.shape)} {src.dtype}")
+    if not table.is_contiguous() or table.numel() * table.element_size() < N * CLIP_DTYPE.itemsize:
+        raise ValueError(f"stage_clips: the table needs {N * CLIP_DTYPE.itemsize} bytes")
+    if status.dtype != torch.int32 or not status.is_contiguous() or status.numel() < N:
+        raise ValueError(f"stage_clips: status is a contiguous int32 tensor of {N} elements")
+    if not (src.device == table.device == x.device == status.device) or not x.is_cuda:
+        raise ValueError("stage_clips: src, table, x and status live on one GPU")
+    d = hip_lib.InputDesc(N, C, T_out, V, src.shape[2], int(src.dtype == torch.float64),
+                          src.shape[0])
+    hip_lib.check(hip_lib.lib().stgcn_input_stage(
+        ctypes.byref(d), hip_lib.ptr(src), hip_lib.ptr(table), hip_lib.ptr(x),
+        hip_lib.ptr(status), hip_lib.stream_handle(x.device)))
+    return x
+
+
+class _Slot:
+    """One staging slot of RaggedDeviceLoader: pinned host and device buffers
+    for the packed frames and the table, and the two events that order its
+    reuse (``copied``: its H2D copies are done; ``free``: the stage kernel that
+    read it is done)."""
+
+    def __init__(self):
+        self.host = self.dev = self.host_table = self.dev_table = None
+        self.copied = self.free = None
+
+
+class RaggedDeviceLoader:
+    """Iterate (x (N, C, T_out, V) fp32 on ``device``, labels int64 on
+    ``device``) from an iterable of batches of items [(clip (T_i, V, C_src),
+    label), ...]. Per batch the host packs the clips into pinned memory
+    (``pack_clips``) and the device pads, augments, casts and transposes
+    (``stage_clips``). Two staging slots: the copies of batch i + 1 run on a
+    side stream while batch i is consumed; the stage kernel waits for its
+    slot's copies, and a slot's next copies wait for the kernel that read it.
+
+    T_out=None: the longest clip of each batch (loopy_pad_collate_fn); a fixed
+    T_out also truncates longer clips to their first T_out frames. augment:
+    per-clip transforms by ``clip_transforms`` (np.random and random, in batch
+    order). out / labels_out (with a fixed T_out): static tensors every batch is
+    written into and that are yielded themselves, e.g. the inputs a GraphedStep
+    captured; each batch then has out.shape[0] clips. An invalid table entry
+    (there is none unless the packing is broken) raises once, after the last
+    batch, from one host read."""
+
+    def __init__(self, batches_of_items, device, V, C, C_src, T_out=None,
+                 src_dtype=torch.float32, augment=False, out=None, labels_out=None):
+        self.batches, self.device = batches_of_items, torch.device(device)
+        self.V, self.C, self.C_src, self.T_out = V, C, C_src, T_out
+        self.src_dtype, self.augment = src_dtype, augment
+        self.np_dtype = _np_dtype(src_dtype)
+        self.out, self.labels_out = out, labels_out
+        if (out is not None or labels_out is not None) and T_out is None:
+            raise ValueError("RaggedDeviceLoader: out / labels_out need a fixed T_out")
+        if out is not None and (tuple(out.shape[1:]) != (C, T_out, V) or
+                                out.dtype != torch.float32 or not out.is_contiguous()):
+            raise ValueError(f"RaggedDeviceLoader: out is a contiguous (N, {C}, {T_out}, {V}) "
+                             "float32 tensor")
+        d = hip_lib.InputDesc(1, C, T_out or 1, V, C_src, int(src_dtype == torch.float64), 1)
+        lib = hip_lib.load_library()
+        if lib.stgcn_input_check(ctypes.byref(d)) != 0:
+            raise ValueError("RaggedDeviceLoader: " +
+                             lib.stgcn_last_error().decode(errors="replace"))
+        self.stream = torch.cuda.Stream(self.device)
+        self.slots = (_Slot(), _Slot())
+
+    def _stage(self, items, slot):
+        """Packs ``items`` into the slot and starts its copies on the side stream."""
+        N = len(items)
+        T_out = self.T_out or max(np.asarray(x).shape[-3] for x, _ in items)
+        need = N * T_out * self.V * self.C_src
+        if slot.copied is not None:
+            slot.copied.synchronize()  # (the pinned buffers: their last copy has left)
+        # The device buffers come from the SIDE stream's pool (as DeviceLoader's do):
+        # their first use is the copy below on that stream, and a block of the
+        # consumer's stream could still be in use by its queued kernels. The stage
+        # kernel's use on the consumer's stream is recorded in __iter__.
+        if slot.host is None or slot.host.numel() < need:
+            slot.host = torch.empty(need, dtype=self.src_dtype).pin_memory()
+            with torch.cuda.stream(self.stream):
+                slot.dev = torch.empty(need, dtype=self.src_dtype, device=self.device)
+        nb = N * CLIP_DTYPE.itemsize
+        if slot.host_table is None or slot.host_table.numel() < nb:
+            slot.host_table = torch.empty(nb, dtype=torch.uint8).pin_memory()
+            with torch.cuda.stream(self.stream):
+                slot.dev_table = torch.empty(nb, dtype=torch.uint8, device=self.device)
+        tr = clip_transforms(N, True) if self.augment else None
+        buf, table, labels = pack_clips(items, T_out, self.C_src, self.np_dtype, out=slot.host,
+                                        transforms=tr)
+        if buf.shape[1] != self.V:
+            raise ValueError(f"RaggedDeviceLoader: clips of {buf.shape[1]} joints, V = {self.V}")
+        slot.host_table.numpy()[:nb] = table.view(np.uint8)
+        yh = torch.from_numpy(labels).pin_memory()
+        with torch.cuda.stream(self.stream):
+            if slot.free is not None:
+                self.stream.wait_event(slot.free)
+            slot.dev[:buf.size].copy_(slot.host[:buf.size], non_blocking=True)
+            slot.dev_table[:nb].copy_(slot.host_table[:nb], non_blocking=True)
+            yd = yh.to(self.device, non_blocking=True)
+            slot.copied = torch.cuda.Event()
+            slot.copied.record(self.stream)
+        return slot, N, T_out, yd
+
+    def __iter__(self):
+        it = iter(self.batches)
+        try:
+            nxt = self._stage(next(it), self.slots[0])
+        except StopIteration:
+            return
+        statuses, i = [], 0
+        while nxt is not None:
+            slot, N, T_out, yd = nxt
+            i += 1
+            try:
+                nxt = self._stage(next(it), self.slots[i % 2])
+            except StopIteration:
+                nxt = None
+            cur = torch.cuda.current_stream(self.device)
+            cur.wait_event(slot.copied)
+            yd.record_stream(cur)
+            slot.dev.record_stream(cur)
+            slot.dev_table.record_stream(cur)
+            if self.out is not None:
+                if self.out.shape[0] != N:
+                    raise ValueError(f"RaggedDeviceLoader: a batch of {N} clips for out of "
+                                     f"{self.out.shape[0]}")
+                x = self.out
+            else:
+                x = torch.empty((N, self.C, T_out, self.V), dtype=torch.float32,
+                                device=self.device)
+            status = torch.empty(N, dtype=torch.int32, device=self.device)
+            cap = slot.dev.numel() // (self.V * self.C_src)
+            src = slot.dev[:cap * self.V * self.C_src].view(cap, self.V, self.C_src)
+            stage_clips(src, slot.dev_table, x, status)
+            slot.free = torch.cuda.Event()
+            slot.free.record(cur)
+            statuses.append(status)
+            if self.labels_out is not None:
+                self.labels_out.copy_(yd)
+                yd = self.labels_out
+            yield x, yd
+        bad = torch.cat(statuses).nonzero().flatten().tolist()  # (the one host read)
+        if bad:
+            raise RuntimeError(f"RaggedDeviceLoader: invalid clip table entries (flat clip "
+                               f"indices {bad[:8]}{' ...' if len(bad) > 8 else ''}): those "
+                               "clips were staged as zeros")

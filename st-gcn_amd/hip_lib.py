@@ -36,6 +36,8 @@ PLAN_X_FROM_U_EVAL = 1024  # ... in the eval forward (stgcn_features: FEATURE_EV
 # stgcn_features bits: additions within ABI 11
 FEATURE_EVAL_CHAIN, FEATURE_EVAL_HEAD = 1, 2
 FEATURE_STEP_STATE = 4  # per-step values from device memory (dropout token, lr, clip)
+FEATURE_INPUT_STAGE = 8  # stgcn_input_check / stgcn_input_stage (data.stage_clips)
+CLIP_APPLY = 1  # stgcn_clip_t.flags bit 0: apply m
 METRICS_WORDS = 8  # 8-byte words of a metrics block before its confusion matrix
 # ABI 7: a y_stats / x_stats block: 5 * C doubles, then STATS_AMAX_WORDS uint32 (max |y|)
 STATS_AMAX_WORDS = 2048
@@ -107,6 +109,16 @@ class AdamTensor(ctypes.Structure):  # ABI 3
                 ("numel", ctypes.c_int64)]
 
 
+class InputDesc(ctypes.Structure):  # stgcn_input_stage (FEATURE_INPUT_STAGE), 32 bytes
+    _fields_ = [("N", _c_int), ("C", _c_int), ("T_out", _c_int), ("V", _c_int),
+                ("C_src", _c_int), ("src_f64", _c_int), ("src_frames", ctypes.c_int64)]
+
+
+class Clip(ctypes.Structure):  # stgcn_clip_t, 48 bytes (numpy: data.CLIP_DTYPE)
+    _fields_ = [("first_frame", ctypes.c_int64), ("frames", _c_int), ("flags", _c_int),
+                ("m", ctypes.c_double * 4)]
+
+
 # Every symbol include/stgcn_hip.h declares (checked by tests/test_capi.py).
 EXPORTED = ("stgcn_abi_version", "stgcn_last_error", "stgcn_check_desc",
             "stgcn_fwd_workspace_bytes", "stgcn_bwd_workspace_bytes",
@@ -119,7 +131,7 @@ EXPORTED = ("stgcn_abi_version", "stgcn_last_error", "stgcn_check_desc",
             "stgcn_eval_metrics_bytes", "stgcn_eval_metrics_reset", "stgcn_head_eval",
             "stgcn_head_eval_u", "stgcn_block_fwd_dseed", "stgcn_block_bwd_dseed",
             "stgcn_seed_next", "stgcn_adam_step_dev2", "stgcn_grad_norm_bytes",
-            "stgcn_grad_norm")
+            "stgcn_grad_norm", "stgcn_input_check", "stgcn_input_stage")
 
 _LIB = None
 
@@ -210,6 +222,10 @@ def load_library(path=LIB_PATH):
     lib.stgcn_fold_prep.argtypes = [ctypes.c_int, ctypes.POINTER(Desc),
                                     ctypes.POINTER(FoldWeights), ctypes.POINTER(_vp), _vp]
     lib.stgcn_fold_prep.restype = ctypes.c_int
+    lib.stgcn_input_check.argtypes = [ctypes.POINTER(InputDesc)]
+    lib.stgcn_input_check.restype = ctypes.c_int
+    lib.stgcn_input_stage.argtypes = [ctypes.POINTER(InputDesc), _vp, _vp, _vp, _vp, _vp]
+    lib.stgcn_input_stage.restype = ctypes.c_int
     if lib.stgcn_abi_version() != ABI_VERSION:
         raise RuntimeError("libstgcn_hip.so ABI version mismatch; rebuild it")
     return lib
