@@ -58,6 +58,8 @@
  *       STGCN_FEATURE_INPUT_STAGE (stgcn_input_stage): x 16 bytes, like a block
  *         tensor; src its element's own 4 (fp32) or 8 (fp64) bytes; the clip
  *         table 8; status 4.
+ *       STGCN_FEATURE_OPTIMIZERS (stgcn_opt_*): the device table 8; every param /
+ *         grad / s0 / s1 / s2 of a table entry, lr_dev, grad_coef and step_dev 4.
  *     A caller with a misaligned read-only input for a 16-byte argument passes an
  *     aligned copy (the Python binding does); torch.empty results are aligned.
  *   - A is (K,V,V), W is (K*C_out, C_in) (the reference's 1x1 Conv2d weight),
@@ -298,6 +300,7 @@ const char *stgcn_last_error(void);
                                     * stgcn_grad_norm                                     */
 #define STGCN_FEATURE_INPUT_STAGE 8 /* stgcn_input_check / stgcn_input_stage: ragged clips
                                     * to the NCTV fp32 input on the device              */
+#define STGCN_FEATURE_OPTIMIZERS 16 /* stgcn_opt_*: AdamW (decoupled decay) and AMSGrad */
 int stgcn_features(void);
 
 /* Validate a descriptor without touching the GPU (0 = supported). */
@@ -562,6 +565,65 @@ int stgcn_adam_step_dev2(const void *dev_table, int ntensors, int64_t total_chun
 size_t stgcn_grad_norm_bytes(int64_t total_chunks);
 int stgcn_grad_norm(const void *dev_table, int ntensors, int64_t total_chunks, double max_norm,
                     double *partials, float *norm_out, float *coef_out, void *stream);
+
+/* ---------------------------------------------------------------------------
+ * STGCN_FEATURE_OPTIMIZERS: the Adam family with decoupled weight decay
+ * (torch.optim.AdamW) and AMSGrad, one launch per table as stgcn_adam_step
+ * (2048 elements per 256-thread block). maximize is not offered.
+ *
+ * stgcn_adam_step's arithmetic (s0 = exp_avg, s1 = exp_avg_sq; every operation
+ * rounded on its own), with
+ *   STGCN_OPT_DECOUPLED_WD: p = p * (float)(1.0 - lr * wd) ahead of the moment
+ *     updates and g left alone (lr the double, or (double)*lr_dev), wd != 0;
+ *   STGCN_OPT_AMSGRAD: vmax = max(vmax, v) (s2 = max_exp_avg_sq) and the
+ *     denominator takes sqrt(vmax).
+ * The three launch forms of stgcn_adam_step / _dev / _dev2 in one call: the step
+ * count is `step` (host, 1-based) or, with step_dev, a device float advanced by
+ * the call (*step_dev += 1 on the stream); the learning rate is `lr` or, with
+ * lr_dev, a device float read when the kernel runs; grad_coef (optional) scales
+ * the gradient, g = grad * *grad_coef, ahead of the weight-decay term. With
+ * neither flag the call gives stgcn_adam_step's bits.
+ *
+ * Alignment: the device table 8 bytes; param, grad, s0, s1, s2, lr_dev,
+ * grad_coef and step_dev 4 (views into a flat bucket work in place). */
+#define STGCN_OPT_ADAM 1 /* stgcn_opt_desc_t.algo (the only one so far) */
+/* stgcn_opt_desc_t.flags */
+#define STGCN_OPT_DECOUPLED_WD 2
+#define STGCN_OPT_AMSGRAD 4
+
+typedef struct stgcn_opt_tensor {
+  float *param;
+  const float *grad;
+  float *s0, *s1, *s2; /* exp_avg, exp_avg_sq, max_exp_avg_sq (null without AMSGrad) */
+  int64_t numel;
+  int32_t flags;       /* 0 */
+  int32_t reserved;    /* 0 */
+} stgcn_opt_tensor_t;
+
+typedef struct stgcn_opt_desc {
+  int32_t algo;          /* STGCN_OPT_ADAM                                      */
+  int32_t flags;
+  double lr;             /* ignored with lr_dev                                 */
+  double beta1, beta2, eps, weight_decay;
+  int64_t step;          /* without step_dev: the 1-based step count            */
+  const float *lr_dev;   /* optional device float: the learning rate            */
+  const float *grad_coef; /* optional device float: g = grad * *grad_coef       */
+  float *step_dev;       /* optional: the device step count                     */
+} stgcn_opt_desc_t;
+
+/* Validates a descriptor on the host (0 = accepted); stgcn_last_error names what
+ * is refused: an unknown algo or flag, a negative lr / weight decay / eps, betas
+ * outside [0, 1), a step < 1 without step_dev, a misaligned device word. */
+int stgcn_opt_check(const stgcn_opt_desc_t *d);
+size_t stgcn_opt_table_bytes(int ntensors);
+/* Fills a HOST buffer (pinned, copied to the device by the caller) with the
+ * tensor list and its chunk prefix sums, as stgcn_adam_build_table does. d says
+ * which state slots must be non-null (s0, s1, and s2 with STGCN_OPT_AMSGRAD). */
+int stgcn_opt_build_table(const stgcn_opt_desc_t *d, const stgcn_opt_tensor_t *tensors,
+                          int ntensors, void *host_table, size_t table_bytes,
+                          int64_t *total_chunks);
+int stgcn_opt_step(const stgcn_opt_desc_t *d, const void *dev_table, int ntensors,
+                   int64_t total_chunks, void *stream);
 
 /* ---------------------------------------------------------------------------
  * STGCN_FEATURE_INPUT_STAGE: the host input pipeline of the reference (loop

@@ -713,7 +713,7 @@ int stgcn_head_fwd_u(const stgcn_head_desc_t *d, const float *U, const float *st
 
 int stgcn_features(void) {
   return STGCN_FEATURE_EVAL_CHAIN | STGCN_FEATURE_EVAL_HEAD | STGCN_FEATURE_STEP_STATE |
-         STGCN_FEATURE_INPUT_STAGE;
+         STGCN_FEATURE_INPUT_STAGE | STGCN_FEATURE_OPTIMIZERS;
 }
 
 // (classes of a metrics block: the head's own LDS limit at C = 1)

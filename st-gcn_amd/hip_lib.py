@@ -37,6 +37,9 @@ PLAN_X_FROM_U_EVAL = 1024  # ... in the eval forward (stgcn_features: FEATURE_EV
 FEATURE_EVAL_CHAIN, FEATURE_EVAL_HEAD = 1, 2
 FEATURE_STEP_STATE = 4  # per-step values from device memory (dropout token, lr, clip)
 FEATURE_INPUT_STAGE = 8  # stgcn_input_check / stgcn_input_stage (data.stage_clips)
+FEATURE_OPTIMIZERS = 16  # stgcn_opt_*: AdamW, AMSGrad (train_ops.FusedAdam / FusedAdamW)
+OPT_ADAM = 1  # stgcn_opt_desc_t.algo
+OPT_DECOUPLED_WD, OPT_AMSGRAD = 2, 4  # stgcn_opt_desc_t.flags
 CLIP_APPLY = 1  # stgcn_clip_t.flags bit 0: apply m
 METRICS_WORDS = 8  # 8-byte words of a metrics block before its confusion matrix
 # ABI 7: a y_stats / x_stats block: 5 * C doubles, then STATS_AMAX_WORDS uint32 (max |y|)
@@ -109,6 +112,19 @@ class AdamTensor(ctypes.Structure):  # ABI 3
                 ("numel", ctypes.c_int64)]
 
 
+class OptTensor(ctypes.Structure):  # stgcn_opt_tensor_t (FEATURE_OPTIMIZERS), 56 bytes
+    _fields_ = [("param", _vp), ("grad", _vp), ("s0", _vp), ("s1", _vp), ("s2", _vp),
+                ("numel", ctypes.c_int64), ("flags", _c_int), ("reserved", _c_int)]
+
+
+class OptDesc(ctypes.Structure):  # stgcn_opt_desc_t
+    _fields_ = [("algo", _c_int), ("flags", _c_int), ("lr", ctypes.c_double),
+                ("beta1", ctypes.c_double), ("beta2", ctypes.c_double),
+                ("eps", ctypes.c_double), ("weight_decay", ctypes.c_double),
+                ("step", ctypes.c_int64), ("lr_dev", _vp), ("grad_coef", _vp),
+                ("step_dev", _vp)]
+
+
 class InputDesc(ctypes.Structure):  # stgcn_input_stage (FEATURE_INPUT_STAGE), 32 bytes
     _fields_ = [("N", _c_int), ("C", _c_int), ("T_out", _c_int), ("V", _c_int),
                 ("C_src", _c_int), ("src_f64", _c_int), ("src_frames", ctypes.c_int64)]
@@ -131,7 +147,8 @@ EXPORTED = ("stgcn_abi_version", "stgcn_last_error", "stgcn_check_desc",
             "stgcn_eval_metrics_bytes", "stgcn_eval_metrics_reset", "stgcn_head_eval",
             "stgcn_head_eval_u", "stgcn_block_fwd_dseed", "stgcn_block_bwd_dseed",
             "stgcn_seed_next", "stgcn_adam_step_dev2", "stgcn_grad_norm_bytes",
-            "stgcn_grad_norm", "stgcn_input_check", "stgcn_input_stage")
+            "stgcn_grad_norm", "stgcn_input_check", "stgcn_input_stage", "stgcn_opt_check",
+            "stgcn_opt_table_bytes", "stgcn_opt_build_table", "stgcn_opt_step")
 
 _LIB = None
 
@@ -207,6 +224,17 @@ def load_library(path=LIB_PATH):
     lib.stgcn_grad_norm.argtypes = [_vp, ctypes.c_int, ctypes.c_int64, ctypes.c_double,
                                     _vp, _vp, _vp, _vp]
     lib.stgcn_grad_norm.restype = ctypes.c_int
+    lib.stgcn_opt_check.argtypes = [ctypes.POINTER(OptDesc)]
+    lib.stgcn_opt_check.restype = ctypes.c_int
+    lib.stgcn_opt_table_bytes.argtypes = [ctypes.c_int]
+    lib.stgcn_opt_table_bytes.restype = ctypes.c_size_t
+    lib.stgcn_opt_build_table.argtypes = [ctypes.POINTER(OptDesc), ctypes.POINTER(OptTensor),
+                                          ctypes.c_int, _vp, ctypes.c_size_t,
+                                          ctypes.POINTER(ctypes.c_int64)]
+    lib.stgcn_opt_build_table.restype = ctypes.c_int
+    lib.stgcn_opt_step.argtypes = [ctypes.POINTER(OptDesc), _vp, ctypes.c_int, ctypes.c_int64,
+                                   _vp]
+    lib.stgcn_opt_step.restype = ctypes.c_int
     lib.stgcn_spatial_workspace_bytes.argtypes = [ctypes.POINTER(SpatialDesc), ctypes.c_int]
     lib.stgcn_spatial_workspace_bytes.restype = ctypes.c_size_t
     lib.stgcn_spatial_fwd.argtypes = [ctypes.POINTER(SpatialDesc)] + [_vp] * 6 + \

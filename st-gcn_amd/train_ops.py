@@ -4,7 +4,8 @@ Linear + cross entropy; lightning_model.py:105-107 and the loss of
 training_step :202) as one autograd Function, and ``FusedAdam``, a drop-in for
 ``torch.optim.Adam`` (lightning_model.py:196-197) whose step is ONE kernel
 launch over every parameter (same hyper-parameters, same per-parameter state
-names ``step`` / ``exp_avg`` / ``exp_avg_sq``, so state_dicts interchange).
+names ``step`` / ``exp_avg`` / ``exp_avg_sq``, so state_dicts interchange),
+with ``FusedAdamW`` and AMSGrad beside it.
 No CPU fallback: both raise without the HIP library / a GPU.
 """
 import ctypes
@@ -208,7 +209,7 @@ def head_eval(y, W, b, labels, topk=1, metrics=None, from_u=None):
 
 
 class FusedAdam(torch.optim.Optimizer):
-    """torch.optim.Adam (amsgrad=False, maximize=False, fp32 parameters on one
+    """torch.optim.Adam (maximize=False, fp32 parameters on one
     device) with the update as one libstgcn_hip launch per step. The tensor
     table (pointers of param / grad / exp_avg / exp_avg_sq) is rebuilt on the
     host only when a pointer changed (e.g. grads re-allocated after
@@ -239,18 +240,25 @@ class FusedAdam(torch.optim.Optimizer):
     ``opt.clip_coef`` are the device tensors of the last step. Unlike
     clip_grad_norm_, ``p.grad`` itself is NOT rescaled: code that reads the
     gradients after the step sees the unclipped ones. Under data parallelism the
-    step runs after the all-reduce, so the norm is the global one."""
+    step runs after the all-reduce, so the norm is the global one.
+
+    amsgrad / decoupled_weight_decay (per group, as torch.optim.Adam's): a group
+    with either takes stgcn_opt_step -- the same arithmetic with p = p * (1 - lr *
+    wd) in place of the gradient's decay term (torch.optim.AdamW) and / or the
+    running maximum ``max_exp_avg_sq`` in the denominator -- in every launch form
+    above. A group with neither takes the calls it always took."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0,
-                 amsgrad=False, capturable=False, max_grad_norm=None):
-        if amsgrad:
-            raise NotImplementedError("FusedAdam: amsgrad")
+                 amsgrad=False, capturable=False, max_grad_norm=None,
+                 decoupled_weight_decay=False):
         if max_grad_norm is not None:
             if not capturable:
                 raise ValueError("FusedAdam: max_grad_norm needs capturable=True")
             if not float(max_grad_norm) > 0:
                 raise ValueError("FusedAdam: max_grad_norm must be positive")
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
+                                      amsgrad=bool(amsgrad),
+                                      decoupled_weight_decay=bool(decoupled_weight_decay)))
         self.capturable = capturable
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         self.grad_norm = self.clip_coef = None  # device tensors (max_grad_norm)
@@ -297,8 +305,14 @@ class FusedAdam(torch.optim.Optimizer):
                     raise RuntimeError("FusedAdam: parameters of a group at different steps")
                 step = steps.pop()
             dev = plist[0].device
-            _, dev_table, nchunks, n, _ = self._table(gi, plist)
             b1, b2 = group["betas"]
+            amsgrad = bool(group.get("amsgrad", False))
+            decoupled = bool(group.get("decoupled_weight_decay", False))
+            if amsgrad or decoupled:
+                self._opt_step(gi, group, plist, amsgrad, decoupled, coef,
+                               dstep if self.capturable else step)
+                continue
+            _, dev_table, nchunks, n, _ = self._table(gi, plist)
             if self.capturable and (torch.is_tensor(lr) or coef is not None):
                 if not torch.is_tensor(lr):  # (a float lr next to clipping)
                     lr = self._lr_tensor(gi, lr, dev)
@@ -316,6 +330,70 @@ class FusedAdam(torch.optim.Optimizer):
                     hip_lib.ptr(dev_table), n, nchunks, group["lr"], b1, b2,
                     group["eps"], group["weight_decay"], step, hip_lib.stream_handle(dev)))
         return loss
+
+    def _opt_step(self, gi, group, plist, amsgrad, decoupled, coef, step):
+        """The group's step through stgcn_opt_step (AMSGrad / decoupled decay);
+        step: the device count (capturable) or this step's host count."""
+        dev = plist[0].device
+        tabs = []
+        for p in plist:
+            st = self.state[p]
+            vmax = None
+            if amsgrad:
+                if "max_exp_avg_sq" not in st:
+                    if torch.cuda.is_current_stream_capturing():
+                        raise RuntimeError("FusedAdam: capture a step only after an eager step "
+                                           "of the same parameters (GraphedStep warm-up)")
+                    st["max_exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                vmax = st["max_exp_avg_sq"]
+                _check_f32(vmax, "max_exp_avg_sq")
+            tabs.append(hip_lib.OptTensor(
+                p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(),
+                st["exp_avg_sq"].data_ptr(), None if vmax is None else vmax.data_ptr(),
+                p.numel(), 0, 0))
+        lr = group["lr"]
+        b1, b2 = group["betas"]
+        flags = (hip_lib.OPT_AMSGRAD if amsgrad else 0) | \
+            (hip_lib.OPT_DECOUPLED_WD if decoupled else 0)
+        desc = hip_lib.OptDesc(
+            hip_lib.OPT_ADAM, flags, 0.0 if torch.is_tensor(lr) else float(lr), b1, b2,
+            group["eps"], group["weight_decay"], 0 if self.capturable else step,
+            hip_lib.ptr(lr) if torch.is_tensor(lr) else None, hip_lib.ptr(coef),
+            hip_lib.ptr(step) if self.capturable else None)
+        _, dev_table, nchunks, n, _ = self._opt_table(gi, desc, tabs, dev)
+        hip_lib.check(hip_lib.lib().stgcn_opt_step(
+            ctypes.byref(desc), hip_lib.ptr(dev_table), n, nchunks, hip_lib.stream_handle(dev)))
+
+    def _opt_table(self, gi, desc, tabs, dev):
+        """_table over stgcn_opt_tensor_t entries (the stgcn_opt_step route): (key,
+        device table, chunks, ntensors, host table) of the OptTensor list
+        ``tabs``; desc: the OptDesc whose state slots the entries must carry."""
+        lib = hip_lib.lib()
+        key = ("opt",) + tuple((t.param, t.grad, t.s0, t.s1, t.s2, t.numel, t.flags) for t in tabs)
+        cached = self._tables.get(gi)
+        if cached is None or cached[0] != key:
+            n = len(tabs)
+            nbytes = lib.stgcn_opt_table_bytes(n)
+            if torch.cuda.is_current_stream_capturing():
+                host = self._spare.pop(gi, None)
+                if host is None or host.numel() < nbytes:
+                    raise RuntimeError("FusedAdam: capture a step only after an eager "
+                                       "step of the same parameters (GraphedStep warm-up)")
+                self._captured.append(host)  # (read by every replay: never freed)
+            else:
+                host = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+                if self.capturable:
+                    self._spare[gi] = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+            chunks = ctypes.c_int64(0)
+            arr = (hip_lib.OptTensor * n)(*tabs)
+            hip_lib.check(lib.stgcn_opt_build_table(
+                ctypes.byref(desc), arr, n,
+                ctypes.c_void_p(host.data_ptr()), nbytes, ctypes.byref(chunks)))
+            dev_table = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            dev_table.copy_(host, non_blocking=True)
+            cached = (key, dev_table, chunks.value, n, host)
+            self._tables[gi] = cached
+        return cached
 
     def _table(self, gi, plist):
         """(key, device table, chunks, ntensors, host table) of the tensors of
@@ -417,6 +495,16 @@ class FusedAdam(torch.optim.Optimizer):
                     st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                 st["step"] = shared
         return shared
+
+
+class FusedAdamW(FusedAdam):
+    """torch.optim.AdamW: FusedAdam with decoupled weight decay (default 1e-2)."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2,
+                 amsgrad=False, capturable=False, max_grad_norm=None):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
+                         amsgrad=amsgrad, capturable=capturable, max_grad_norm=max_grad_norm,
+                         decoupled_weight_decay=True)
 
 
 class GraphedStep:
