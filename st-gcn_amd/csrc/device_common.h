@@ -1,5 +1,11 @@
-// Device helpers shared by the fp32 (kernels.hip) and bf16 (kernels_bf16.hip)
-// GEMM kernels of libstgcn_hip.so. gfx950 only.
+// Device helpers shared by every kernel file of libstgcn_hip.so. gfx950 only.
+//
+// The one home of the hand-counted, hazard-sensitive primitives: the vector
+// types, the MFMA wrappers, bf16 / fp16 packing and operand splits, buffer
+// resources, LDS-DMA and the explicit waits (first half of this file), then the
+// reductions and the conv tile epilogues. A kernel file keeps a variant of its
+// own only where the variant's point is what differs (e.g. a wait that names
+// the staging registers it protects).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -11,9 +17,76 @@
 namespace stgcn {
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
+typedef float floatx4 __attribute__((ext_vector_type(4)));
+typedef int int4v __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 __device__ __forceinline__ floatx16 mfma32(float a, float b, floatx16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
+}
+
+// v_mfma_f32_32x32x16_bf16; operand fragments as bf16x8 or as the 16 bytes a
+// ds_read_b128 returned
+__device__ __forceinline__ floatx16 mfma_bf16(bf16x8 a, bf16x8 b, floatx16 c) {
+  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+}
+__device__ __forceinline__ floatx16 mfma_bf16(uint4 a, uint4 b, floatx16 c) {
+  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a),
+                                                 __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+}
+// v_mfma_f32_32x32x16_f16 on fp16 operands carried in the same 16-byte
+// fragment registers as the bf16 ones
+__device__ __forceinline__ floatx16 mfma_h(bf16x8 a, bf16x8 b, floatx16 c) {
+  return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a),
+                                                __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+}
+
+// two floats -> one dword of two bf16 (round to nearest even, v_cvt_pk_bf16_f32),
+// and the two halves of such a dword back as floats
+__host__ __device__ __forceinline__ unsigned pk_bf16(float a, float b) {
+  const bf16x2 v = {(__bf16)a, (__bf16)b};
+  return __builtin_bit_cast(unsigned, v);
+}
+__device__ __forceinline__ float lo_f(unsigned w) { return __builtin_bit_cast(float, w << 16); }
+__device__ __forceinline__ float hi_f(unsigned w) {
+  return __builtin_bit_cast(float, w & 0xffff0000u);
+}
+// the same for fp16 (round to nearest even)
+__host__ __device__ __forceinline__ unsigned pk_f16(float a, float b) {
+  typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
+  const h2_t v = {(_Float16)a, (_Float16)b};
+  return __builtin_bit_cast(unsigned, v);
+}
+__device__ __forceinline__ float lo_h(unsigned w) {
+  return (float)__builtin_bit_cast(_Float16, (unsigned short)(w & 0xffffu));
+}
+__device__ __forceinline__ float hi_h(unsigned w) {
+  return (float)__builtin_bit_cast(_Float16, (unsigned short)(w >> 16));
+}
+
+// Operand splits of two floats (a, b) into packed pairs, round to nearest even
+// at each step; the differences are exact fp32.
+// 2-way bf16: x == h + m to 2^-16
+__device__ __forceinline__ void split_bf16x2(float a, float b, unsigned &h, unsigned &m) {
+  h = pk_bf16(a, b);
+  m = pk_bf16(a - lo_f(h), b - hi_f(h));
+}
+// 3-way bf16, exact: x == h + m + l (the last residual holds at most 7
+// significant bits; kernels_x3.hip has the argument)
+__device__ __forceinline__ void split_bf16x3(float a, float b, unsigned &h, unsigned &m,
+                                             unsigned &l) {
+  h = pk_bf16(a, b);
+  const float ra = a - lo_f(h), rb = b - hi_f(h);
+  m = pk_bf16(ra, rb);
+  l = pk_bf16(ra - lo_f(m), rb - hi_f(m));
+}
+// 2-way fp16 split of two (scaled) floats: x = h + l to 2^-22
+__device__ __forceinline__ void splith2(float a, float b, unsigned &h, unsigned &l) {
+  h = pk_f16(a, b);
+  l = pk_f16(a - lo_h(h), b - hi_h(h));
 }
 
 __device__ __forceinline__ double wave_sum(double v) {
@@ -102,15 +175,107 @@ __device__ __forceinline__ void block_sum2_atomic(double a, double b, double *ds
 // lds_wave_base must be the same for the whole wave.
 constexpr unsigned kOOB = 0x80000000u;
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const float *base, int64_t nfloats) {
-  int64_t bytes = nfloats * 4;
+// Size field of a buffer resource: clamped below 2^31, so that kOOB (and every
+// offset past a longer tensor's first 2 GiB) stays out of range. SIGNED: sizes
+// computed as "what is left" may be negative (a chunk past the last channel)
+// and give an empty resource.
+template <bool SIGNED = false>
+__device__ __forceinline__ int rsrc_size(int64_t bytes) {
   if (bytes > 0x7fffffffLL) bytes = 0x7fffffffLL;
-  return __builtin_amdgcn_make_buffer_rsrc((void *)base, 0, (int)bytes, 0x00020000);
+  if (SIGNED && bytes < 0) bytes = 0;
+  return (int)bytes;
 }
+// Raw buffer resource over [base, base + bytes), for the buffer builtins ...
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc_bytes(const void *base,
+                                                                  int64_t bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc((void *)base, 0, rsrc_size(bytes), 0x00020000);
+}
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const float *base, int64_t nfloats) {
+  return make_rsrc_bytes(base, nfloats * 4);
+}
+// ... and the same four words for the "s" operand of an inline-asm buffer_load
+__device__ __forceinline__ int4v make_rsrc_words(const void *base, int64_t bytes) {
+  const uint64_t a = reinterpret_cast<uint64_t>(base);
+  const int size = rsrc_size<true>(bytes);
+  return int4v{(int)(uint32_t)a, (int)((a >> 32) & 0xffff), size, 0x00020000};
+}
+// After a resource is built in SGPRs by SALU / v_readfirstlane and before the
+// first inline-asm buffer_load that reads it: the assembler text is opaque to
+// the compiler's hazard recogniser, so the wait states between the SGPR writes
+// and the VMEM read are spent here by hand.
+__device__ __forceinline__ void rsrc_hazard_nop() { asm volatile("s_nop 4" ::: "memory"); }
 
 __device__ __forceinline__ void blds_f32(__amdgpu_buffer_rsrc_t rs, unsigned voff,
                                          float *lds_wave_base) {
   __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, lds_wave_base, 4, voff, 0, 0, 0);
+}
+
+// LDS-DMA of one 4-byte / 16-byte piece per lane: LDS[m0v + 4 | 16 * lane] =
+// mem[voff] (offsets past the resource, kOOB: 0). m0v, the wave's LDS byte
+// address, must be wave-uniform (an "s" operand: apply readfirstlane where the
+// compiler cannot prove it). Inline asm and not the builtin above: hipcc treats
+// an LDS-DMA builtin as a pending LDS write and waits for it (vmcnt) before the
+// next ds_read of ANY buffer, which would drain a prefetch every step; these
+// are neither counted nor waited for, so the caller waits with an explicit
+// s_waitcnt vmcnt (wait_vm and friends below). m0 is saved and restored because
+// the compiler keeps its own value there across the asm; the s_nop 0 is the
+// wait state between the SALU write of m0 and the LDS-DMA that reads it.
+__device__ __forceinline__ void lds_dma_b32(int4v rs, unsigned voff, unsigned m0v) {
+  unsigned keep;
+  asm volatile(
+      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\t"
+      "buffer_load_dword %2, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
+      : "=&s"(keep)
+      : "s"(m0v), "v"(voff), "s"(rs)
+      : "memory");
+}
+__device__ __forceinline__ void lds_dma_b128(int4v rs, unsigned voff, unsigned m0v) {
+  unsigned keep;
+  asm volatile(
+      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\t"
+      "buffer_load_dwordx4 %2, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
+      : "=&s"(keep)
+      : "s"(m0v), "v"(voff), "s"(rs)
+      : "memory");
+}
+
+// Explicit waits for the loads above. This wave's LDS writes and reads done
+// (lgkmcnt(0)), then the workgroup barrier ...
+__device__ __forceinline__ void wait_lgkm_barrier() {
+  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+}
+// ... and with at most N of this wave's VMEM operations (DMA included) left in
+// flight first
+template <int N>
+__device__ __forceinline__ void wait_vm_barrier() {
+  asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory");
+}
+// s_waitcnt vmcnt(n) for a run-time n (the count is an immediate, so a switch).
+// Two dispatches, kept apart because merging them changes the code of their
+// kernels: wait_vm takes the exact counts its callers pass (compile-time after
+// unrolling; any other count waits for everything) ...
+__device__ __forceinline__ void wait_vm(int n) {
+  switch (n) {
+#define STGCN_WAIT_VM(c, n) \
+  case c: asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n) : "memory"); break;
+    STGCN_WAIT_VM(0, 0) STGCN_WAIT_VM(3, 3) STGCN_WAIT_VM(4, 4) STGCN_WAIT_VM(6, 6)
+    STGCN_WAIT_VM(7, 7) STGCN_WAIT_VM(9, 9) STGCN_WAIT_VM(10, 10) STGCN_WAIT_VM(12, 12)
+    STGCN_WAIT_VM(13, 13) STGCN_WAIT_VM(15, 15) STGCN_WAIT_VM(16, 16)
+    default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
+  }
+}
+// ... wait_vm_floor4 takes any count and waits for 4 q, n rounded down to a
+// multiple of 4 (at most 60): waiting for up to 3 more instructions than asked
+// is safe and keeps the run-time dispatch to a 16-way branch tree
+__device__ __forceinline__ void wait_vm_floor4(int n) {
+  const int q = n < 0 ? 0 : (n > 63 ? 15 : n >> 2);
+  switch (q) {
+    STGCN_WAIT_VM(0, 0) STGCN_WAIT_VM(1, 4) STGCN_WAIT_VM(2, 8) STGCN_WAIT_VM(3, 12)
+    STGCN_WAIT_VM(4, 16) STGCN_WAIT_VM(5, 20) STGCN_WAIT_VM(6, 24) STGCN_WAIT_VM(7, 28)
+    STGCN_WAIT_VM(8, 32) STGCN_WAIT_VM(9, 36) STGCN_WAIT_VM(10, 40) STGCN_WAIT_VM(11, 44)
+    STGCN_WAIT_VM(12, 48) STGCN_WAIT_VM(13, 52) STGCN_WAIT_VM(14, 56) STGCN_WAIT_VM(15, 60)
+#undef STGCN_WAIT_VM
+  }
 }
 
 __host__ __device__ constexpr int round64(int x) { return (x + 63) & ~63; }

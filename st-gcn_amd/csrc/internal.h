@@ -223,7 +223,7 @@ hipError_t launch_fold_grads(const float *slab, int S, const float *scratch, con
                              const double *Tq, int R, int C, int V, float *dwc, float *dWt,
                              float *dW, hipStream_t s);
 // k_bn_relu_bwd_apply that also writes the clip-chunk sums of dU,
-// cs[z][C][L] for z < apply_cols_chunks(N) (kernels.hip)
+// cs[z][C][L] for z < apply_cols_chunks(N) (kernels_bn.hip)
 int apply_cols_chunks(int N);
 hipError_t launch_bn_relu_bwd_apply_cols(const float *dy, const float *U, const float *mean,
                                          const float *invstd, const float *g, const float *b,

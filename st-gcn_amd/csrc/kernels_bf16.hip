@@ -26,37 +26,10 @@
 
 namespace stgcn {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef int int4v __attribute__((ext_vector_type(4)));
-
-// One 4-byte LDS-DMA piece per lane: LDS[lds_wave + 4 lane] = src[voff] (kOOB
-// -> 0). Inline asm, so hipcc neither counts it nor waits for it before LDS
-// reads of other buffers (the caller waits with an explicit s_waitcnt vmcnt).
-__device__ __forceinline__ void dma_b32(int4v rs, unsigned voff, unsigned lds_wave) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\t"
-      "buffer_load_dword %2, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "s"(__builtin_amdgcn_readfirstlane(lds_wave)), "v"(voff), "s"(rs)
-      : "memory");
-}
 // (wave-uniform values the compiler cannot prove uniform, for "s" operands)
 __device__ __forceinline__ int4v uniform4(int4v v) {
   return int4v{__builtin_amdgcn_readfirstlane(v.x), __builtin_amdgcn_readfirstlane(v.y),
                __builtin_amdgcn_readfirstlane(v.z), __builtin_amdgcn_readfirstlane(v.w)};
-}
-
-__device__ __forceinline__ floatx16 mfma_bf16(bf16x8 a, bf16x8 b, floatx16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-
-// two floats -> one dword of two bf16 (round to nearest even, v_cvt_pk_bf16_f32)
-__device__ __forceinline__ unsigned pk_bf16(float a, float b) {
-  const bf16x2 v = {(__bf16)a, (__bf16)b};
-  return __builtin_bit_cast(unsigned, v);
 }
 
 // 4 consecutive bf16 elements starting at element e (stored as bf16; byte offset
@@ -577,20 +550,21 @@ __global__ __launch_bounds__((WgBf16Geo<NQ, V, SIN, FT, CB>::NTH), 1) void k_wgr
     const uint64_t sq = reinterpret_cast<uint64_t>(reinterpret_cast<const __bf16 *>(p.Q) +
                                                    (int64_t)n * p.q_bstride);
     const int4v rp = uniform4(int4v{(int)(uint32_t)sp, (int)((sp >> 32) & 0xffff),
-                               (int)std::min<int64_t>(p.p_bstride * 2, 0x7fffffff), 0x00020000});
+                               rsrc_size(p.p_bstride * 2), 0x00020000});
     const int4v rq = uniform4(int4v{(int)(uint32_t)sq, (int)((sq >> 32) & 0xffff),
-                               (int)std::min<int64_t>(p.q_bstride * 2, 0x7fffffff), 0x00020000});
+                               rsrc_size(p.q_bstride * 2), 0x00020000});
     const int t0 = SIN * m0 + p.off;
     const unsigned lb =
         (unsigned)__builtin_amdgcn_readfirstlane((int)(lds_addr + (unsigned)(bufi * G::BUF)));
-    asm volatile("s_nop 4" ::: "memory");  // descriptor SGPRs -> buffer_load
+    rsrc_hazard_nop();
 #pragma unroll
     for (int i = 0; i < PR; ++i)
       if (i * G::NW + wave < PRN) {
         const unsigned e = ptab[i];
         const bool ok = e != ~0u && m0 + (int)(e >> 26) < p.M;
         const unsigned voff = ok ? ((e & 0x3ffffffu) + (unsigned)(m0 * V)) * 2u : kOOB;
-        dma_b32(rp, voff, lb + (unsigned)((i * G::NW + wave) * 256));
+        lds_dma_b32(rp, voff,
+                    __builtin_amdgcn_readfirstlane(lb + (unsigned)((i * G::NW + wave) * 256)));
       }
 #pragma unroll
     for (int i = 0; i < QR; ++i)
@@ -599,7 +573,8 @@ __global__ __launch_bounds__((WgBf16Geo<NQ, V, SIN, FT, CB>::NTH), 1) void k_wgr
         const int t = t0 + (int)(e >> 26);
         const bool ok = e != ~0u && t >= 0 && t < p.T_src;
         const unsigned voff = ok ? (unsigned)((int)(e & 0x3ffffffu) + t0 * V) * 2u : kOOB;
-        dma_b32(rq, voff, lb + (unsigned)(G::PBYTES + (i * G::NW + wave) * 256));
+        lds_dma_b32(rq, voff,
+                    __builtin_amdgcn_readfirstlane(lb + (unsigned)(G::PBYTES + (i * G::NW + wave) * 256)));
       }
   };
 
@@ -631,7 +606,7 @@ __global__ __launch_bounds__((WgBf16Geo<NQ, V, SIN, FT, CB>::NTH), 1) void k_wgr
       for (int it = 0, itm = it0; itm < it1; ++it, ++itm) {
         // item it landed (every wave's pieces), and every wave is done reading
         // item it-1's buffer, which item it+1's pieces overwrite
-        asm volatile("s_waitcnt vmcnt(0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        wait_vm_barrier<0>();
         if (itm + 1 < it1) dma_stage(itm + 1, (it + 1) & 1);
         compute(acc, lds + (it & 1) * G::BUF, nt_c, std::integral_constant<int, 0>{},
                 std::integral_constant<int, G::KSTEPS>{});
@@ -743,20 +718,21 @@ __global__ __launch_bounds__(512, 1) void k_wgrad_bf16_raw(WgradParams p) {
     const uint64_t sq = reinterpret_cast<uint64_t>(reinterpret_cast<const __bf16 *>(p.Q) +
                                                    (int64_t)n * p.q_bstride);
     const int4v rp = uniform4(int4v{(int)(uint32_t)sp, (int)((sp >> 32) & 0xffff),
-                                    (int)std::min<int64_t>(p.p_bstride * 2, 0x7fffffff), 0x00020000});
+                                    rsrc_size(p.p_bstride * 2), 0x00020000});
     const int4v rq = uniform4(int4v{(int)(uint32_t)sq, (int)((sq >> 32) & 0xffff),
-                                    (int)std::min<int64_t>(p.q_bstride * 2, 0x7fffffff), 0x00020000});
+                                    rsrc_size(p.q_bstride * 2), 0x00020000});
     const int t0 = m0 - 4;
     const unsigned lb =
         (unsigned)__builtin_amdgcn_readfirstlane((int)(lds_addr + (unsigned)(bufi * G::BUF)));
-    asm volatile("s_nop 4" ::: "memory");  // descriptor SGPRs -> buffer_load
+    rsrc_hazard_nop();
 #pragma unroll
     for (int i = 0; i < G::PR; ++i)
       if (i * G::NW + wave < G::PRN) {
         const unsigned e = ptab[i];
         const bool ok = e != ~0u && m0 + (int)(e >> 23) < p.M;
         const unsigned voff = ok ? ((e & 0x7fffffu) + (unsigned)(m0 * G::V)) * 2u : kOOB;
-        dma_b32(rp, voff, lb + (unsigned)((i * G::NW + wave) * 256));
+        lds_dma_b32(rp, voff,
+                    __builtin_amdgcn_readfirstlane(lb + (unsigned)((i * G::NW + wave) * 256)));
       }
 #pragma unroll
     for (int i = 0; i < G::QR; ++i)
@@ -765,7 +741,8 @@ __global__ __launch_bounds__(512, 1) void k_wgrad_bf16_raw(WgradParams p) {
         const int t = t0 + (int)(e >> 23);
         const bool ok = e != ~0u && t >= 0 && t < p.T_src;
         const unsigned voff = ok ? (unsigned)((int)(e & 0x7fffffu) + t0 * G::V) * 2u : kOOB;
-        dma_b32(rq, voff, lb + (unsigned)(G::PBYTES + (i * G::NW + wave) * 256));
+        lds_dma_b32(rq, voff,
+                    __builtin_amdgcn_readfirstlane(lb + (unsigned)(G::PBYTES + (i * G::NW + wave) * 256)));
       }
   };
 
@@ -819,7 +796,7 @@ __global__ __launch_bounds__(512, 1) void k_wgrad_bf16_raw(WgradParams p) {
     };
     if (it0 < it1) stage(it0, 0);
     for (int it = 0, itm = it0; itm < it1; ++it, ++itm) {
-      asm volatile("s_waitcnt vmcnt(0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+      wait_vm_barrier<0>();
       if (itm + 1 < it1) stage(itm + 1, (it + 1) & 1);
       compute(lds + (it & 1) * G::BUF);
     }
@@ -924,10 +901,9 @@ __global__ __launch_bounds__((WgGemmGeo<TR, TC>::NTH), 1) void k_wgrad_gemm_bf16
       for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
   // 8 consecutive fp32 -> bf16x8, as two 16-byte LDS reads (fragment rows are
   // 16-byte aligned; element-wise reads compiled to b96 + b32 pieces)
-  typedef float f32x4v __attribute__((ext_vector_type(4)));
   auto frag = [&](const float *src) {
-    const f32x4v *v = reinterpret_cast<const f32x4v *>(__builtin_assume_aligned(src, 16));
-    const f32x4v l4 = v[0], h4 = v[1];
+    const floatx4 *v = reinterpret_cast<const floatx4 *>(__builtin_assume_aligned(src, 16));
+    const floatx4 l4 = v[0], h4 = v[1];
     return bf16x8{(__bf16)l4.x, (__bf16)l4.y, (__bf16)l4.z, (__bf16)l4.w,
                   (__bf16)h4.x, (__bf16)h4.y, (__bf16)h4.z, (__bf16)h4.w};
   };

@@ -49,9 +49,7 @@ namespace stgcn {
 //        summed in LDS in tap order, in fp64): dW' = sum_q Wt_q^T dWc_q and
 //        sum_{n,t} dZ = sum_q Wt_q^T Tq.
 // Up to three jobs share a launch (blockIdx.x runs over their tiles).
-typedef float float16v __attribute__((ext_vector_type(16)));
 typedef float float8v __attribute__((ext_vector_type(8)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 typedef double double4v __attribute__((ext_vector_type(4)));
 
 __host__ __device__ inline int pad32(int x) { return (x + 31) & ~31; }

@@ -37,18 +37,6 @@
 
 namespace stgcn {
 
-typedef __bf16 bf16x8f __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2f __attribute__((ext_vector_type(2)));
-typedef int int4f __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ floatx16 mfma_bf(bf16x8f a, bf16x8f b, floatx16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ unsigned pkbf(float a, float b) {
-  const bf16x2f v = {(__bf16)a, (__bf16)b};
-  return __builtin_bit_cast(unsigned, v);
-}
-
 template <int V, int K>
 struct SpFwdGeo {
   static constexpr int FT = kTileCols / V;
@@ -149,9 +137,9 @@ __global__ __launch_bounds__(256, 2) void k_sp_fwd_bf16(SpFwdParams P) {
   auto load_x = [&](int chunk) {
     const int64_t rem = (int64_t)(P.C - chunk * G::CK) * TV * 4;
     const uint64_t src = xsrc + (uint64_t)chunk * G::CK * TV * 4;
-    const int4f rs = {(int)(uint32_t)src, (int)((src >> 32) & 0xffff),
-                      (int)(rem > 0x7fffffff ? 0x7fffffff : (rem > 0 ? rem : 0)), 0x00020000};
-    asm volatile("s_nop 4" ::: "memory");
+    const int4v rs = {(int)(uint32_t)src, (int)((src >> 32) & 0xffff), rsrc_size<true>(rem),
+                      0x00020000};
+    rsrc_hazard_nop();
 #pragma unroll
     for (int k = 0; k < G::IPT; ++k)
       asm volatile("buffer_load_dword %0, %1, %2, 0 offen"
@@ -207,7 +195,7 @@ __global__ __launch_bounds__(256, 2) void k_sp_fwd_bf16(SpFwdParams P) {
   // before unrelated LDS reads); completion by the s_waitcnt before write_x
   const uint64_t wsrc =
       reinterpret_cast<uint64_t>(P.wpk) + (uint64_t)rt * nch * G::W_BYTES;
-  const int4f rsw = {(int)(uint32_t)wsrc, (int)((wsrc >> 32) & 0xffff), nch * G::W_BYTES,
+  const int4v rsw = {(int)(uint32_t)wsrc, (int)((wsrc >> 32) & 0xffff), nch * G::W_BYTES,
                      0x00020000};
   const unsigned ldsw = (unsigned)reinterpret_cast<uintptr_t>(lds + G::OFF_W);
   auto dma_w = [&](int chunk, int buf) {
@@ -215,13 +203,7 @@ __global__ __launch_bounds__(256, 2) void k_sp_fwd_bf16(SpFwdParams P) {
     for (int d = wave; d < 2 * K; d += 4) {
       const unsigned voffw = (unsigned)(chunk * G::W_BYTES + d * 1024 + lane * 16);
       const unsigned m0v = ldsw + (unsigned)(buf * G::W_BYTES + d * 1024);
-      unsigned keep;
-      asm volatile(
-          "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\t"
-          "buffer_load_dwordx4 %2, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
-          : "=&s"(keep)
-          : "s"(m0v), "v"(voffw), "s"(rsw)
-          : "memory");
+      lds_dma_b128(rsw, voffw, m0v);
     }
   };
 
@@ -268,11 +250,11 @@ __global__ __launch_bounds__(256, 2) void k_sp_fwd_bf16(SpFwdParams P) {
         const int bo2 = ((gct * 32 + lo) * G::XP + 8 * hi) * 2;
 #pragma unroll
         for (int s = 0; s < G::KS; ++s) {
-          const bf16x8f a = *reinterpret_cast<const bf16x8f *>(xi + xo + s * 32);
-          const bf16x8f bh = *reinterpret_cast<const bf16x8f *>(ah + bo2 + s * 32);
-          const bf16x8f bm = *reinterpret_cast<const bf16x8f *>(am + bo2 + s * 32);
-          ga = mfma_bf(a, bh, ga);
-          ga = mfma_bf(a, bm, ga);
+          const bf16x8 a = *reinterpret_cast<const bf16x8 *>(xi + xo + s * 32);
+          const bf16x8 bh = *reinterpret_cast<const bf16x8 *>(ah + bo2 + s * 32);
+          const bf16x8 bm = *reinterpret_cast<const bf16x8 *>(am + bo2 + s * 32);
+          ga = mfma_bf16(a, bh, ga);
+          ga = mfma_bf16(a, bm, ga);
         }
         const int col = gct * 32 + lo;
         const int kk = col / V, v = col - kk * V;
@@ -283,8 +265,8 @@ __global__ __launch_bounds__(256, 2) void k_sp_fwd_bf16(SpFwdParams P) {
             const int t = row >> 4, ch0 = row & 15;
             if (t < G::FT) {
               uint2 d;
-              d.x = pkbf(ga[4 * q], ga[4 * q + 1]);
-              d.y = pkbf(ga[4 * q + 2], ga[4 * q + 3]);
+              d.x = pk_bf16(ga[4 * q], ga[4 * q + 1]);
+              d.y = pk_bf16(ga[4 * q + 2], ga[4 * q + 3]);
               *reinterpret_cast<uint2 *>(gi + ((t * V + v) * G::SLOTS) * 16 +
                                          (kk * 16 + ch0) * 2) = d;
             }
@@ -332,11 +314,11 @@ __global__ __launch_bounds__(256, 2) void k_sp_fwd_bf16(SpFwdParams P) {
       const char *gi = lds + G::OFF_G;
 #pragma unroll
       for (int k = 0; k < K; ++k) {
-        const bf16x8f a = *reinterpret_cast<const bf16x8f *>(wa + k * 2048);
+        const bf16x8 a = *reinterpret_cast<const bf16x8 *>(wa + k * 2048);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          const bf16x8f b = *reinterpret_cast<const bf16x8f *>(gi + bo[j] + k * 32);
-          acc[j] = mfma_bf(a, b, acc[j]);
+          const bf16x8 b = *reinterpret_cast<const bf16x8 *>(gi + bo[j] + k * 32);
+          acc[j] = mfma_bf16(a, b, acc[j]);
         }
       }
     }
@@ -435,8 +417,8 @@ __global__ __launch_bounds__(512, 1) void k_sp_fwd_wide(SpFwdParams P) {
   auto load_x = [&](int chunk) {
     const int64_t rem = (int64_t)(P.C - chunk * G::CK) * TV * 4;
     const uint64_t src = xsrc + (uint64_t)chunk * G::CK * TV * 4;
-    const int4f rs = {(int)(uint32_t)src, (int)((src >> 32) & 0xffff),
-                      (int)(rem > 0x7fffffff ? 0x7fffffff : (rem > 0 ? rem : 0)), 0x00020000};
+    const int4v rs = {(int)(uint32_t)src, (int)((src >> 32) & 0xffff), rsrc_size<true>(rem),
+                      0x00020000};
     unsigned goff[G::IPT];
 #pragma unroll
     for (int k = 0; k < G::IPT; ++k) {
@@ -444,7 +426,7 @@ __global__ __launch_bounds__(512, 1) void k_sp_fwd_wide(SpFwdParams P) {
       const int ch = e / G::NCOLS, pos = e - ch * G::NCOLS;
       goff[k] = (e < G::NIT && pos < pos_lim) ? (unsigned)((ch * TV + m0 * V + pos) * 4) : kOOB;
     }
-    asm volatile("s_nop 4" ::: "memory");
+    rsrc_hazard_nop();
 #pragma unroll
     for (int k = 0; k < G::IPT; ++k)
       asm volatile("buffer_load_dword %0, %1, %2, 0 offen"
@@ -505,7 +487,7 @@ __global__ __launch_bounds__(512, 1) void k_sp_fwd_wide(SpFwdParams P) {
     }
   };
   const uint64_t wsrc = reinterpret_cast<uint64_t>(P.wpk);
-  const int4f rsw = {(int)(uint32_t)wsrc, (int)((wsrc >> 32) & 0xffff), nch * G::W_BYTES,
+  const int4v rsw = {(int)(uint32_t)wsrc, (int)((wsrc >> 32) & 0xffff), nch * G::W_BYTES,
                      0x00020000};
   const unsigned ldsw = (unsigned)reinterpret_cast<uintptr_t>(lds + G::OFF_W);
   auto dma_w = [&](int chunk, int buf) {
@@ -513,13 +495,7 @@ __global__ __launch_bounds__(512, 1) void k_sp_fwd_wide(SpFwdParams P) {
     for (int d = wave; d < G::W_BYTES / 1024; d += 8) {
       const unsigned voffw = (unsigned)(chunk * G::W_BYTES + d * 1024 + lane * 16);
       const unsigned m0v = ldsw + (unsigned)(buf * G::W_BYTES + d * 1024);
-      unsigned keep;
-      asm volatile(
-          "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\t"
-          "buffer_load_dwordx4 %2, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
-          : "=&s"(keep)
-          : "s"(m0v), "v"(voffw), "s"(rsw)
-          : "memory");
+      lds_dma_b128(rsw, voffw, m0v);
     }
   };
 
@@ -570,11 +546,11 @@ __global__ __launch_bounds__(512, 1) void k_sp_fwd_wide(SpFwdParams P) {
         const int bo2 = ((gct * 32 + lo) * G::XP + 8 * hi) * 2;
 #pragma unroll
         for (int s = 0; s < G::KS; ++s) {
-          const bf16x8f xa = *reinterpret_cast<const bf16x8f *>(xi + xo + s * 32);
-          const bf16x8f bh = *reinterpret_cast<const bf16x8f *>(ah + bo2 + s * 32);
-          const bf16x8f bm = *reinterpret_cast<const bf16x8f *>(am + bo2 + s * 32);
-          ga = mfma_bf(xa, bh, ga);
-          ga = mfma_bf(xa, bm, ga);
+          const bf16x8 xa = *reinterpret_cast<const bf16x8 *>(xi + xo + s * 32);
+          const bf16x8 bh = *reinterpret_cast<const bf16x8 *>(ah + bo2 + s * 32);
+          const bf16x8 bm = *reinterpret_cast<const bf16x8 *>(am + bo2 + s * 32);
+          ga = mfma_bf16(xa, bh, ga);
+          ga = mfma_bf16(xa, bm, ga);
         }
         const int col = gct * 32 + lo;
         const int kk = col / V, v = col - kk * V;
@@ -585,8 +561,8 @@ __global__ __launch_bounds__(512, 1) void k_sp_fwd_wide(SpFwdParams P) {
             const int t = row >> 4, ch0 = row & 15;
             if (t < G::FT) {
               uint2 d;
-              d.x = pkbf(ga[4 * q], ga[4 * q + 1]);
-              d.y = pkbf(ga[4 * q + 2], ga[4 * q + 3]);
+              d.x = pk_bf16(ga[4 * q], ga[4 * q + 1]);
+              d.y = pk_bf16(ga[4 * q + 2], ga[4 * q + 3]);
               *reinterpret_cast<uint2 *>(gi + ((t * V + v) * G::SLOTS) * 16 + (kk * 16 + ch0) * 2) =
                   d;
             }
@@ -601,16 +577,16 @@ __global__ __launch_bounds__(512, 1) void k_sp_fwd_wide(SpFwdParams P) {
       const char *gi = lds + G::OFF_G;
 #pragma unroll
       for (int k = 0; k < K; ++k) {
-        bf16x8f a[G::MB], b[2];
+        bf16x8 a[G::MB], b[2];
 #pragma unroll
         for (int rb = 0; rb < G::MB; ++rb)
-          a[rb] = *reinterpret_cast<const bf16x8f *>(wa + k * 2 * ROWS * 16 + ao[rb]);
+          a[rb] = *reinterpret_cast<const bf16x8 *>(wa + k * 2 * ROWS * 16 + ao[rb]);
 #pragma unroll
-        for (int j = 0; j < 2; ++j) b[j] = *reinterpret_cast<const bf16x8f *>(gi + bo[j] + k * 32);
+        for (int j = 0; j < 2; ++j) b[j] = *reinterpret_cast<const bf16x8 *>(gi + bo[j] + k * 32);
 #pragma unroll
         for (int rb = 0; rb < G::MB; ++rb)
 #pragma unroll
-          for (int j = 0; j < 2; ++j) acc[rb][j] = mfma_bf(a[rb], b[j], acc[rb][j]);
+          for (int j = 0; j < 2; ++j) acc[rb][j] = mfma_bf16(a[rb], b[j], acc[rb][j]);
       }
     }
     if (more) {
@@ -917,11 +893,11 @@ template <int D>
 __device__ __forceinline__ void gk_ring_wait(int ahead) {
   static_assert(2 * D < 64, "vmcnt range");
   if (ahead >= 2)
-    asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::"n"(2 * D) : "memory");
+    wait_vm_barrier<2 * D>();
   else if (ahead == 1)
-    asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::"n"(D) : "memory");
+    wait_vm_barrier<D>();
   else
-    asm volatile("s_waitcnt vmcnt(0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    wait_vm_barrier<0>();
 }
 
 template <int TR>
@@ -1021,14 +997,13 @@ __global__ __launch_bounds__(512, 1) void k_wgrad_gemm_gk(WgradParams p) {
     // MFMAs (element-wise reads compiled to b96 + b32 pieces, each waited on
     // before its conversion: the loop was LDS-latency bound)
     constexpr int NKS = G::KC / 16;
-    typedef float f32x4v __attribute__((ext_vector_type(4)));
-    f32x4v pf[NKS][2][2];
-    bf16x8f b[NKS][2];
+    floatx4 pf[NKS][2][2];
+    bf16x8 b[NKS][2];
 #pragma unroll
     for (int s = 0; s < NKS; ++s)
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
-        const f32x4v *src = reinterpret_cast<const f32x4v *>(
+        const floatx4 *src = reinterpret_cast<const floatx4 *>(
             __builtin_assume_aligned(pa + i * 32 * G::PITCH + 16 * s, 16));
         pf[s][i][0] = src[0];
         pf[s][i][1] = src[1];
@@ -1037,20 +1012,20 @@ __global__ __launch_bounds__(512, 1) void k_wgrad_gemm_gk(WgradParams p) {
     for (int s = 0; s < NKS; ++s)
 #pragma unroll
       for (int j = 0; j < 2; ++j)
-        b[s][j] = *reinterpret_cast<const bf16x8f *>(qb + j * 32 * 5 * 16 + s * 32);
+        b[s][j] = *reinterpret_cast<const bf16x8 *>(qb + j * 32 * 5 * 16 + s * 32);
 #pragma unroll
     for (int s = 0; s < NKS; ++s) {
-      bf16x8f a[2];
+      bf16x8 a[2];
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
-        const f32x4v lo4 = pf[s][i][0], hi4 = pf[s][i][1];
-        a[i] = bf16x8f{(__bf16)lo4.x, (__bf16)lo4.y, (__bf16)lo4.z, (__bf16)lo4.w,
+        const floatx4 lo4 = pf[s][i][0], hi4 = pf[s][i][1];
+        a[i] = bf16x8{(__bf16)lo4.x, (__bf16)lo4.y, (__bf16)lo4.z, (__bf16)lo4.w,
                        (__bf16)hi4.x, (__bf16)hi4.y, (__bf16)hi4.z, (__bf16)hi4.w};
       }
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = mfma_bf(a[i], b[s][j], acc[i][j]);
+        for (int j = 0; j < 2; ++j) acc[i][j] = mfma_bf16(a[i], b[s][j], acc[i][j]);
     }
   }
   float *slab = p.slab + (int64_t)split * p.R * p.C;

@@ -45,70 +45,12 @@
 
 namespace stgcn {
 
-typedef __bf16 spb_bf8 __attribute__((ext_vector_type(8)));
-typedef __bf16 spb_bf2 __attribute__((ext_vector_type(2)));
-typedef int spb_i4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ unsigned spb_pk(float a, float b) {
-  const spb_bf2 v = {(__bf16)a, (__bf16)b};
-  return __builtin_bit_cast(unsigned, v);
-}
-// (a, b) -> packed bf16 h and bf16 of the residual m (a == h + m to 2^-16)
-__device__ __forceinline__ void spb_split(float a, float b, unsigned &h, unsigned &m) {
-  h = spb_pk(a, b);
-  m = spb_pk(a - __builtin_bit_cast(float, h << 16),
-             b - __builtin_bit_cast(float, h & 0xffff0000u));
-}
-__device__ __forceinline__ floatx16 spb_mfma(uint4 a, uint4 b, floatx16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(spb_bf8, a),
-                                                 __builtin_bit_cast(spb_bf8, b), c, 0, 0, 0);
-}
-// buffer resource for inline-asm loads (base, bytes)
-__device__ __forceinline__ spb_i4 spb_rsrc(const void *base, int64_t bytes) {
-  const uint64_t a = reinterpret_cast<uint64_t>(base);
-  if (bytes > 0x7fffffffLL) bytes = 0x7fffffffLL;
-  if (bytes < 0) bytes = 0;
-  return spb_i4{(int)(uint32_t)a, (int)((a >> 32) & 0xffff), (int)bytes, 0x00020000};
-}
-// 16-byte LDS-DMA of this lane's piece: LDS[m0 + 16 lane] = mem[voff] (past the
-// resource: 0).
-// Inline asm so the compiler does not wait for it before unrelated LDS reads.
-__device__ __forceinline__ void spb_dma16(spb_i4 rs, unsigned voff, unsigned m0v) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\t"
-      "buffer_load_dwordx4 %2, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "s"(m0v), "v"(voff), "s"(rs)
-      : "memory");
-}
-// s_waitcnt vmcnt(n) for the counts this kernel uses (immediates only)
-__device__ __forceinline__ void spb_wait_vm(int n) {
-  switch (n) {
-    case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-    case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-    case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-    case 7: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
-    case 9: asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); break;
-    case 10: asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); break;
-    case 12: asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); break;
-    case 13: asm volatile("s_waitcnt vmcnt(13)" ::: "memory"); break;
-    case 15: asm volatile("s_waitcnt vmcnt(15)" ::: "memory"); break;
-    case 16: asm volatile("s_waitcnt vmcnt(16)" ::: "memory"); break;
-    default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-  }
-}
-__device__ __forceinline__ void spb_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-
 // 8 floats -> the two operand planes h, m
 __device__ __forceinline__ void spb_planes(const float (&v)[8], uint4 (&o)[2]) {
-  spb_split(v[0], v[1], o[0].x, o[1].x);
-  spb_split(v[2], v[3], o[0].y, o[1].y);
-  spb_split(v[4], v[5], o[0].z, o[1].z);
-  spb_split(v[6], v[7], o[0].w, o[1].w);
+  split_bf16x2(v[0], v[1], o[0].x, o[1].x);
+  split_bf16x2(v[2], v[3], o[0].y, o[1].y);
+  split_bf16x2(v[4], v[5], o[0].z, o[1].z);
+  split_bf16x2(v[6], v[7], o[0].w, o[1].w);
 }
 
 // The bf16 path: bf16 W', fp32 dZ rounded to bf16; H and A to 2^-16 (two planes).
@@ -202,9 +144,9 @@ __global__ __launch_bounds__(512, 1) void k_sp_bwd_fused(SpBwdParams P) {
     reinterpret_cast<unsigned *>(lds + G::OFF_XB + G::NPOS * G::XBP)[e] = 0u;
   __syncthreads();  // (full drain: the table loads are ordinary loads)
   {
-    const spb_i4 ra = spb_rsrc(P.aimg, G::AIMG_BYTES);
+    const int4v ra = make_rsrc_words(P.aimg, G::AIMG_BYTES);
     for (int i = wave; i < G::AIMG_BYTES / 1024; i += 8)
-      spb_dma16(ra, (unsigned)(i * 1024 + lane * 16), lds0 + G::OFF_A + i * 1024);
+      lds_dma_b128(ra, (unsigned)(i * 1024 + lane * 16), lds0 + G::OFF_A + i * 1024);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   }
 
@@ -218,16 +160,16 @@ __global__ __launch_bounds__(512, 1) void k_sp_bwd_fused(SpBwdParams P) {
     ft = r % P.nft;
     n = r / P.nft;
   };
-  const spb_i4 rw = spb_rsrc(P.wpk, (int64_t)P.ncb * NCH * G::W_BYTES);
+  const int4v rw = make_rsrc_words(P.wpk, (int64_t)P.ncb * NCH * G::W_BYTES);
   // issue cursor: the next chunk to DMA (item ik of this workgroup, chunk ic, ring
   // slot islot); the item's dZ resource, first-row offset and W' base are formed
   // once per item (no run-time divisions per chunk)
   int ik = 0, ic = 0, islot = 0, irow = 0, iwb = 0;
-  spb_i4 rz;
+  int4v rz;
   auto start_item = [&]() {
     int n = 0, ft = 0, cb = 0;
     if (ik < myitems) decode(first + ik * NG, n, ft, cb);
-    rz = spb_rsrc(P.dZ + (int64_t)n * P.R * TV, (int64_t)P.R * TV * 4);
+    rz = make_rsrc_words(P.dZ + (int64_t)n * P.R * TV, (int64_t)P.R * TV * 4);
     irow = ft * G::FT * V;
     iwb = cb * NCH * G::W_BYTES;
   };
@@ -241,11 +183,11 @@ __global__ __launch_bounds__(512, 1) void k_sp_bwd_fused(SpBwdParams P) {
       const int start = irow + r * TV;  // from the 16-byte boundary below: the row's shift
       const unsigned voff = (unsigned)(((start & ~3) + 4 * lane) * 4);
       if (lane < G::NPC)
-        spb_dma16(rz, voff, lds0 + G::OFF_RING + islot * G::RING_SLOT + r * G::RP * 4);
+        lds_dma_b128(rz, voff, lds0 + G::OFF_RING + islot * G::RING_SLOT + r * G::RP * 4);
     }
     if (lane < G::WPW)
-      spb_dma16(rw, (unsigned)(iwb + ic * G::W_BYTES + wave * G::WPW * 16 + lane * 16),
-                lds0 + G::OFF_W + islot * G::W_BYTES + wave * G::WPW * 16);
+      lds_dma_b128(rw, (unsigned)(iwb + ic * G::W_BYTES + wave * G::WPW * 16 + lane * 16),
+                   lds0 + G::OFF_W + islot * G::W_BYTES + wave * G::WPW * 16);
     islot = islot + 1 == D ? 0 : islot + 1;
     irow += G::CR * TV;
     if (++ic == NCH) {
@@ -259,13 +201,13 @@ __global__ __launch_bounds__(512, 1) void k_sp_bwd_fused(SpBwdParams P) {
     int n, ft, cb;
     decode(item, n, ft, cb);
     const int p0 = ft * G::FT * V;
-    const spb_i4 rx = spb_rsrc(P.x + (int64_t)n * P.C * TV, (int64_t)P.C * TV * 4);
+    const int4v rx = make_rsrc_words(P.x + (int64_t)n * P.C * TV, (int64_t)P.C * TV * 4);
 #pragma unroll
     for (int h = 0; h < 4; ++h) {
       const int r = 4 * wave + h;
       const int start = (cb * G::CB + r) * TV + p0;
       const unsigned voff = (unsigned)(((start & ~3) + 4 * lane) * 4);
-      if (lane < G::NPC) spb_dma16(rx, voff, lds0 + G::OFF_X + r * G::RP * 4);
+      if (lane < G::NPC) lds_dma_b128(rx, voff, lds0 + G::OFF_X + r * G::RP * 4);
     }
   };
 
@@ -297,8 +239,8 @@ __global__ __launch_bounds__(512, 1) void k_sp_bwd_fused(SpBwdParams P) {
       // each) and, in an item's first D - 1 chunks, its x slice (4, issued
       // after the previous item's row pass)
       const int after = 3 * min(D - 2, nchunks - 1 - gch) + (k > 0 && c <= D - 2 ? 4 : 0);
-      spb_wait_vm(after);
-      spb_barrier();  // chunk gch in LDS for every wave; chunk gch - 1 retired
+      wait_vm(after);
+      wait_lgkm_barrier();  // chunk gch in LDS for every wave; chunk gch - 1 retired
       if (gch + D - 1 < nchunks) issue_chunk();
       const int slot = gch % D;
       // A operand: dZ[r = 8 hi + j][frame f, joint lo] (0 past V: read at a
@@ -313,15 +255,15 @@ __global__ __launch_bounds__(512, 1) void k_sp_bwd_fused(SpBwdParams P) {
       for (int j = 0; j < 8; ++j) dv[j] = rz[j * G::RP + ((j * TV) & 3)];
 #pragma unroll
       for (int j = 0; j < 8; ++j) dv[j] = lo < V ? dv[j] : 0.f;
-      a.x = spb_pk(dv[0], dv[1]);
-      a.y = spb_pk(dv[2], dv[3]);
-      a.z = spb_pk(dv[4], dv[5]);
-      a.w = spb_pk(dv[6], dv[7]);
+      a.x = pk_bf16(dv[0], dv[1]);
+      a.y = pk_bf16(dv[2], dv[3]);
+      a.z = pk_bf16(dv[4], dv[5]);
+      a.w = pk_bf16(dv[6], dv[7]);
 #pragma unroll
       for (int kk = 0; kk < K; ++kk) {
         const uint4 w = *reinterpret_cast<const uint4 *>(wb + kk * 1024);
-        T[kk] = spb_mfma(a, w, T[kk]);  // [v][ci] = sum_r dZ[r][v] W_k[r][ci]
-        S[kk] = spb_mfma(w, a, S[kk]);  // [ci][v]
+        T[kk] = mfma_bf16(a, w, T[kk]);  // [v][ci] = sum_r dZ[r][v] W_k[r][ci]
+        S[kk] = mfma_bf16(w, a, S[kk]);  // [ci][v]
       }
     }
 
@@ -345,9 +287,9 @@ __global__ __launch_bounds__(512, 1) void k_sp_bwd_fused(SpBwdParams P) {
 #pragma unroll
           for (int p = 0; p < G::NPLA; ++p)
             am[p] = *reinterpret_cast<const uint4 *>(aim + ((kk * 2 + ks) * G::NPLA + p) * 1024);
-          dxp[kk] = spb_mfma(am[0], b[0], dxp[kk]);
-          dxp[kk] = spb_mfma(am[1], b[0], dxp[kk]);
-          dxp[kk] = spb_mfma(am[0], b[1], dxp[kk]);
+          dxp[kk] = mfma_bf16(am[0], b[0], dxp[kk]);
+          dxp[kk] = mfma_bf16(am[1], b[0], dxp[kk]);
+          dxp[kk] = mfma_bf16(am[0], b[1], dxp[kk]);
         }
       floatx16 dxa = dxp[0];
 #pragma unroll
@@ -358,7 +300,7 @@ __global__ __launch_bounds__(512, 1) void k_sp_bwd_fused(SpBwdParams P) {
         if (w < V) st[lo * G::SP + f * V + w] = dxa[i];
       }
     }
-    spb_barrier();  // dx row image complete (the x slice landed with the item's chunk waits)
+    wait_lgkm_barrier();  // dx row image complete (the x slice landed with the item's chunk waits)
 
     // ---- row pass, 16 threads per channel: ReLU mask, BN1 sums, dx store, and
     // f(BN1(x)) into the dA operand image (row (frame, w), slot of ci; bf16)
@@ -435,7 +377,7 @@ __global__ __launch_bounds__(512, 1) void k_sp_bwd_fused(SpBwdParams P) {
         }
       }
     }
-    spb_barrier();  // f(BN1(x)) image complete; the x slice and dx row image free
+    wait_lgkm_barrier();  // f(BN1(x)) image complete; the x slice and dx row image free
     if (k + 1 < myitems) issue_x(first + (k + 1) * NG);
 
     // ---- dA_k[v][w] += sum_ci H_k[ci][v] f(BN1(x))[ci][w] (this frame's 32 channels)
@@ -452,8 +394,8 @@ __global__ __launch_bounds__(512, 1) void k_sp_bwd_fused(SpBwdParams P) {
           for (int j = 0; j < 8; ++j) sv[j] = S[kk][8 * ks + j];
           uint4 sp[2];
           spb_planes(sv, sp);
-          dacc[kk] = spb_mfma(sp[0], xv, dacc[kk]);
-          dacc[kk] = spb_mfma(sp[1], xv, dacc[kk]);
+          dacc[kk] = mfma_bf16(sp[0], xv, dacc[kk]);
+          dacc[kk] = mfma_bf16(sp[1], xv, dacc[kk]);
         }
       }
     }
@@ -593,20 +535,6 @@ struct Sp50Params {
   PrevBn prev;
 };
 
-// s_waitcnt vmcnt(q) for a run-time n, q = n rounded down to a multiple of 4
-// (at most 60): waiting for up to 3 more instructions than asked is safe and
-// keeps the dispatch to a 16-way branch tree
-__device__ __forceinline__ void sp50_wait_vm(int n) {
-  const int q = n < 0 ? 0 : (n > 63 ? 15 : n >> 2);
-  switch (q) {
-#define SP50_W(i) \
-  case i: asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * i) : "memory"); break;
-    SP50_W(0) SP50_W(1) SP50_W(2) SP50_W(3) SP50_W(4) SP50_W(5) SP50_W(6) SP50_W(7)
-    SP50_W(8) SP50_W(9) SP50_W(10) SP50_W(11) SP50_W(12) SP50_W(13) SP50_W(14) SP50_W(15)
-#undef SP50_W
-  }
-}
-
 // Shared chunk pipeline of the two kernels: the ring of dZ chunks (2 rows per
 // wave) and W' chunks (1/8 per wave), 3 DMA instructions per wave and chunk.
 template <int K>
@@ -615,17 +543,17 @@ struct Sp50Ring {
   const Sp50Params &P;
   unsigned lds0;
   int ring_off, w_off, first, NG, NCH, TV, wave, lane, myitems;
-  spb_i4 rw;
+  int4v rw;
   // issue cursor: the next chunk to DMA (item ik of this workgroup, chunk ic,
   // ring slot islot); the item's dZ resource, first-row offset and W' base are
   // formed once per item (no divisions per chunk)
   int ik = 0, ic = 0, islot = 0, irow = 0, iwb = 0;
-  spb_i4 rz;
+  int4v rz;
   __device__ Sp50Ring(const Sp50Params &P_, unsigned lds0_, int ring_off_, int w_off_, int first_,
                       int wave_, int lane_, int myitems_)
       : P(P_), lds0(lds0_), ring_off(ring_off_), w_off(w_off_), first(first_), NG(gridDim.x),
         NCH(P_.R / 16), TV(P_.T * 50), wave(wave_), lane(lane_), myitems(myitems_) {
-    rw = spb_rsrc(P.wpk, (int64_t)P.ncb * NCH * G::W_BYTES);
+    rw = make_rsrc_words(P.wpk, (int64_t)P.ncb * NCH * G::W_BYTES);
     start_item();
   }
   __device__ void decode(int it, int &n, int &ft, int &cb) const {
@@ -637,7 +565,7 @@ struct Sp50Ring {
   __device__ void start_item() {
     int n = 0, ft = 0, cb = 0;
     if (ik < myitems) decode(first + ik * NG, n, ft, cb);
-    rz = spb_rsrc(P.dZ + (int64_t)n * P.R * TV, (int64_t)P.R * TV * 4);
+    rz = make_rsrc_words(P.dZ + (int64_t)n * P.R * TV, (int64_t)P.R * TV * 4);
     irow = ft * G::NPOS;  // element offset of chunk ic's row 0 (rows of a chunk TV apart)
     iwb = cb * NCH * G::W_BYTES;
   }
@@ -648,12 +576,12 @@ struct Sp50Ring {
       const int r = 2 * wave + h;
       const int start = irow + r * TV;  // from the 16-byte boundary below
       if (lane < G::NPC)
-        spb_dma16(rz, (unsigned)(((start & ~3) + 4 * lane) * 4),
-                  lds0 + ring_off + islot * G::RING_SLOT + r * G::RP * 4);
+        lds_dma_b128(rz, (unsigned)(((start & ~3) + 4 * lane) * 4),
+                     lds0 + ring_off + islot * G::RING_SLOT + r * G::RP * 4);
     }
     if (lane < G::WPW)
-      spb_dma16(rw, (unsigned)(iwb + ic * G::W_BYTES + wave * G::WPW * 16 + lane * 16),
-                lds0 + w_off + islot * G::W_BYTES + wave * G::WPW * 16);
+      lds_dma_b128(rw, (unsigned)(iwb + ic * G::W_BYTES + wave * G::WPW * 16 + lane * 16),
+                   lds0 + w_off + islot * G::W_BYTES + wave * G::WPW * 16);
     islot = islot + 1 == G::D ? 0 : islot + 1;
     irow += G::CR * TV;
     if (++ic == NCH) {
@@ -675,10 +603,10 @@ struct Sp50Ring {
 #pragma unroll
     for (int j = 0; j < 8; ++j) dv[j] = v < 50 ? dv[j] : 0.f;
     uint4 a;
-    a.x = spb_pk(dv[0], dv[1]);
-    a.y = spb_pk(dv[2], dv[3]);
-    a.z = spb_pk(dv[4], dv[5]);
-    a.w = spb_pk(dv[6], dv[7]);
+    a.x = pk_bf16(dv[0], dv[1]);
+    a.y = pk_bf16(dv[2], dv[3]);
+    a.z = pk_bf16(dv[4], dv[5]);
+    a.w = pk_bf16(dv[6], dv[7]);
     return a;
   }
 };
@@ -707,9 +635,9 @@ __global__ __launch_bounds__(512, 1) void k_sp50_dx(Sp50Params P) {
   const float pmu = pv ? P.prev.mean[c] : 0.f, pis = pv ? P.prev.invstd[c] : 1.f;
   const float pa = pv ? pis * P.prev.g[c] : 1.f, pb = pv ? P.prev.b[c] : 0.f;
   {  // A image (48 KiB) by LDS-DMA
-    const spb_i4 ra = spb_rsrc(P.aimg, G::AIMG);
+    const int4v ra = make_rsrc_words(P.aimg, G::AIMG);
     for (int i = wave; i < G::AIMG / 1024; i += 8)
-      spb_dma16(ra, (unsigned)(i * 1024 + lane * 16), lds0 + i * 1024);
+      lds_dma_b128(ra, (unsigned)(i * 1024 + lane * 16), lds0 + i * 1024);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   }
   // x (prev mode: the previous block's U) of this lane's 16 (frame f, joint w)
@@ -726,7 +654,7 @@ __global__ __launch_bounds__(512, 1) void k_sp50_dx(Sp50Params P) {
   auto load_x = [&](int item) {
     int n, ft, cbb;
     ring.decode(item, n, ft, cbb);
-    const spb_i4 rx = spb_rsrc(P.x + (int64_t)n * P.C * TV, (int64_t)P.C * TV * 4);
+    const int4v rx = make_rsrc_words(P.x + (int64_t)n * P.C * TV, (int64_t)P.C * TV * 4);
 #pragma unroll
     for (int gq = 0; gq < 4; ++gq)
 #pragma unroll
@@ -773,8 +701,8 @@ __global__ __launch_bounds__(512, 1) void k_sp50_dx(Sp50Params P) {
         for (int i = 0; i < 16; ++i) T[kk][vt][i] = 0.f;
     // ---- T_k = H_k^T = dZ^T W_k over the chunks, both joint tiles
     for (int cc = 0; cc < NCH; ++cc, ++gch) {
-      sp50_wait_vm(issued - mk[0]);
-      spb_barrier();  // chunk gch in LDS for every wave; chunk gch - 1 retired
+      wait_vm_floor4(issued - mk[0]);
+      wait_lgkm_barrier();  // chunk gch in LDS for every wave; chunk gch - 1 retired
 #pragma unroll
       for (int i = 0; i < D - 2; ++i) mk[i] = mk[i + 1];
       if (gch + D - 1 < nchunks) {
@@ -790,8 +718,8 @@ __global__ __launch_bounds__(512, 1) void k_sp50_dx(Sp50Params P) {
 #pragma unroll
       for (int kk = 0; kk < K; ++kk) {
         const uint4 w = *reinterpret_cast<const uint4 *>(wb + kk * 1024);
-        T[kk][0] = spb_mfma(a0, w, T[kk][0]);  // [v][ci] = sum_r dZ[r][v] W_k[r][ci]
-        T[kk][1] = spb_mfma(a1, w, T[kk][1]);
+        T[kk][0] = mfma_bf16(a0, w, T[kk][0]);  // [v][ci] = sum_r dZ[r][v] W_k[r][ci]
+        T[kk][1] = mfma_bf16(a1, w, T[kk][1]);
       }
     }
     // ---- dx^T[w][ci] = sum_k sum_v A_k[v][w] H_k^T[v][ci], w in tile wt
@@ -812,12 +740,12 @@ __global__ __launch_bounds__(512, 1) void k_sp50_dx(Sp50Params P) {
           const int fr = (((kk * 2 + wt) * 2 + vt) * 2 + ks) * 2;
           const uint4 am0 = *reinterpret_cast<const uint4 *>(aim + fr * 1024);
           const uint4 am1 = *reinterpret_cast<const uint4 *>(aim + (fr + 1) * 1024);
-          dxa = spb_mfma(am0, bpl[0], dxa);
-          dxa = spb_mfma(am1, bpl[0], dxa);
-          dxa = spb_mfma(am0, bpl[1], dxa);
+          dxa = mfma_bf16(am0, bpl[0], dxa);
+          dxa = mfma_bf16(am1, bpl[0], dxa);
+          dxa = mfma_bf16(am0, bpl[1], dxa);
         }
     // ---- row pass on the registers: lane = channel c, joints w of frame f
-    sp50_wait_vm(issued - mark_x);
+    wait_vm_floor4(issued - mark_x);
     asm volatile("" : "+v"(xr[0]), "+v"(xr[1]), "+v"(xr[2]), "+v"(xr[3]), "+v"(xr[4]),
                  "+v"(xr[5]), "+v"(xr[6]), "+v"(xr[7]), "+v"(xr[8]), "+v"(xr[9]), "+v"(xr[10]),
                  "+v"(xr[11]), "+v"(xr[12]), "+v"(xr[13]), "+v"(xr[14]), "+v"(xr[15]));
@@ -853,7 +781,7 @@ __global__ __launch_bounds__(512, 1) void k_sp50_dx(Sp50Params P) {
     d1 += s1;
     d2 += s2;
     if (P.write_dx) {  // (dx stores: masked positions go past the clip's resource)
-      const spb_i4 rdx = spb_rsrc(P.dx + (int64_t)n * P.C * TV, (int64_t)P.C * TV * 4);
+      const int4v rdx = make_rsrc_words(P.dx + (int64_t)n * P.C * TV, (int64_t)P.C * TV * 4);
 #pragma unroll
       for (int gq = 0; gq < 4; ++gq)
 #pragma unroll
@@ -924,7 +852,7 @@ __global__ __launch_bounds__(512, 1) void k_sp50_dA(Sp50Params P) {
   auto load_x = [&](int item) {
     int n, ft, cbb;
     ring.decode(item, n, ft, cbb);
-    const spb_i4 rx = spb_rsrc(P.x + (int64_t)n * P.C * TV, (int64_t)P.C * TV * 4);
+    const int4v rx = make_rsrc_words(P.x + (int64_t)n * P.C * TV, (int64_t)P.C * TV * 4);
     const int64_t base = (int64_t)c * TV + (int64_t)ft * G::NPOS;
     const int live = min(G::NPOS, TV - ft * G::NPOS);
 #pragma unroll
@@ -977,8 +905,8 @@ __global__ __launch_bounds__(512, 1) void k_sp50_dA(Sp50Params P) {
       for (int i = 0; i < 16; ++i) S[kk][i] = 0.f;
     // ---- S_k = H_k = W_k^T dZ over the chunks (joint tile vt)
     for (int cc = 0; cc < NCH; ++cc, ++gch) {
-      sp50_wait_vm(issued - mk[0]);
-      spb_barrier();
+      wait_vm_floor4(issued - mk[0]);
+      wait_lgkm_barrier();
 #pragma unroll
       for (int i = 0; i < D - 2; ++i) mk[i] = mk[i + 1];
       if (gch + D - 1 < nchunks) {
@@ -993,11 +921,11 @@ __global__ __launch_bounds__(512, 1) void k_sp50_dA(Sp50Params P) {
 #pragma unroll
       for (int kk = 0; kk < K; ++kk) {
         const uint4 w = *reinterpret_cast<const uint4 *>(wb + kk * 1024);
-        S[kk] = spb_mfma(w, bz, S[kk]);  // [ci][v] = sum_r W_k[r][ci] dZ[r][v]
+        S[kk] = mfma_bf16(w, bz, S[kk]);  // [ci][v] = sum_r W_k[r][ci] dZ[r][v]
       }
     }
     // ---- f(BN1(x)) of the item into the image (row (frame, w) = position)
-    sp50_wait_vm(issued - mark_x);
+    wait_vm_floor4(issued - mark_x);
     asm volatile("" : "+v"(xr[0]), "+v"(xr[1]), "+v"(xr[2]), "+v"(xr[3]), "+v"(xr[4]),
                  "+v"(xr[5]), "+v"(xr[6]), "+v"(xr[7]), "+v"(xr[8]), "+v"(xr[9]), "+v"(xr[10]),
                  "+v"(xr[11]), "+v"(xr[12]));
@@ -1019,7 +947,7 @@ __global__ __launch_bounds__(512, 1) void k_sp50_dA(Sp50Params P) {
         }
       }
     }
-    spb_barrier();  // f(BN1(x)) image complete
+    wait_lgkm_barrier();  // f(BN1(x)) image complete
     if (k + 1 < myitems) {
       load_x(item + NG);
       issued += NQ;
@@ -1044,8 +972,8 @@ __global__ __launch_bounds__(512, 1) void k_sp50_dA(Sp50Params P) {
         spb_planes(sv, sp);
 #pragma unroll
         for (int wt = 0; wt < 2; ++wt) {
-          dacc[kk][wt] = spb_mfma(sp[0], xv[wt], dacc[kk][wt]);
-          dacc[kk][wt] = spb_mfma(sp[1], xv[wt], dacc[kk][wt]);
+          dacc[kk][wt] = mfma_bf16(sp[0], xv[wt], dacc[kk][wt]);
+          dacc[kk][wt] = mfma_bf16(sp[1], xv[wt], dacc[kk][wt]);
         }
       }
     }

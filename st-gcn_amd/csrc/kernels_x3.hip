@@ -49,54 +49,14 @@ constexpr int kWgWriteStart = 1;
 
 namespace stgcn {
 
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef int int4v __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ floatx16 mfma_x(bf16x8_t a, bf16x8_t b, floatx16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
 typedef float f2v __attribute__((ext_vector_type(2)));
-// fp16 operands carried in the same 16-byte fragment registers (NPL = 2)
-__device__ __forceinline__ floatx16 mfma_h(bf16x8_t a, bf16x8_t b, floatx16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a),
-                                                __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
-}
 // the plane products of one MFMA: bf16 (NPL = 1, 3) or fp16 (NPL = 2)
 template <int NPL>
-__device__ __forceinline__ floatx16 mfma_p(bf16x8_t a, bf16x8_t b, floatx16 c) {
+__device__ __forceinline__ floatx16 mfma_p(bf16x8 a, bf16x8 b, floatx16 c) {
   if constexpr (NPL == 2)
     return mfma_h(a, b, c);
   else
-    return mfma_x(a, b, c);
-}
-
-__host__ __device__ __forceinline__ unsigned pk2(float a, float b) {
-  const bf16x2_t v = {(__bf16)a, (__bf16)b};
-  return __builtin_bit_cast(unsigned, v);
-}
-__device__ __forceinline__ float lo_f(unsigned w) { return __builtin_bit_cast(float, w << 16); }
-__device__ __forceinline__ float hi_f(unsigned w) {
-  return __builtin_bit_cast(float, w & 0xffff0000u);
-}
-
-__host__ __device__ __forceinline__ unsigned pkh2(float a, float b) {
-  typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
-  const h2_t v = {(_Float16)a, (_Float16)b};
-  return __builtin_bit_cast(unsigned, v);
-}
-__device__ __forceinline__ float lo_h(unsigned w) {
-  return (float)__builtin_bit_cast(_Float16, (unsigned short)(w & 0xffffu));
-}
-__device__ __forceinline__ float hi_h(unsigned w) {
-  return (float)__builtin_bit_cast(_Float16, (unsigned short)(w >> 16));
-}
-// 2-way fp16 split of two (scaled) floats: x = h + l to 2^-22 (RNE twice)
-__device__ __forceinline__ void splith2(float a, float b, unsigned &h, unsigned &l) {
-  h = pkh2(a, b);
-  l = pkh2(a - lo_h(h), b - hi_h(h));
+    return mfma_bf16(a, b, c);
 }
 
 // Power-of-two operand scale of the fp16 splits: max |x| (float bits in *amax)
@@ -110,14 +70,6 @@ __device__ __forceinline__ int f16x2_se(const unsigned *amax) {
   return se < -100 ? -100 : (se > 100 ? 100 : se);
 }
 __device__ __forceinline__ float pow2f(int e) { return __builtin_bit_cast(float, (unsigned)(e + 127) << 23); }
-
-// exact 3-way split of two floats into packed (h, m, l) bf16 pairs
-__device__ __forceinline__ void split2(float a, float b, unsigned &h, unsigned &m, unsigned &l) {
-  h = pk2(a, b);
-  const float ra = a - lo_f(h), rb = b - hi_f(h);
-  m = pk2(ra, rb);
-  l = pk2(ra - lo_f(m), rb - hi_f(m));
-}
 
 // Waits until at most NA VMEM operations are in flight, naming the 16 window
 // staging registers (so no consumer of them is scheduled above the wait).
@@ -279,7 +231,7 @@ __device__ __forceinline__ void spb_epilogue(const ConvGemmParams &p, floatx16 (
   const uint64_t xsrc = reinterpret_cast<uint64_t>(p.sx + (int64_t)n * C * cT);
   const int64_t xbytes = (int64_t)C * cT * 4;
   const int4v rsx = {(int)(uint32_t)xsrc, (int)((xsrc >> 32) & 0xffff),
-                     (int)(xbytes > 0x7fffffff ? 0x7fffffff : xbytes), 0x00020000};
+                     rsrc_size(xbytes), 0x00020000};
   const bool pv = p.prev.mean != nullptr;
   const int combo = tid / NSUB, sub = tid - combo * NSUB;
   const int vb = combo / 3, wb = combo - (combo / 3) * 3;
@@ -326,20 +278,14 @@ __device__ __forceinline__ void spb_epilogue(const ConvGemmParams &p, floatx16 (
   for (int h = 0; h < MR; ++h) {
     __syncthreads();  // every wave is done with the main loop's buffers / the last half
     // (the x rows' DMA first: its latency runs under the H image and table writes)
-    asm volatile("s_nop 4" ::: "memory");  // descriptor SGPRs -> buffer_load
+    rsrc_hazard_nop();
     for (int rr = wave; rr < (MR == 1 ? 0 : 64); rr += 8) {
       const int c = r0 + h * 64 + rr;
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         const unsigned voff = (c < C && coff[k] != kOOB) ? ((unsigned)(c * cT) + coff[k]) * 4u : kOOB;
         const unsigned m0v = (unsigned)reinterpret_cast<uintptr_t>(Ximg + rr * P + k * 64);
-        unsigned keep;
-        asm volatile(
-            "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\t"
-            "buffer_load_dword %2, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
-            : "=&s"(keep)
-            : "s"(m0v), "v"(voff), "s"(rsx)
-            : "memory");
+        lds_dma_b32(rsx, voff, m0v);
       }
     }
     if (MR == 1 || mi == h) {
@@ -748,9 +694,9 @@ __global__ __launch_bounds__(NW * 64, (NPL == 1 || NW == 4) ? 2 : 1) void k_conv
     const int64_t rem = (int64_t)(p.C - chunk * G::CK) * cstride * esz;
     const uint64_t src = reinterpret_cast<uint64_t>(p.in) +
                          (uint64_t)(((int64_t)n * p.in_bstride + (int64_t)chunk * G::CK * cstride) * esz);
-    const int4v rs = {(int)(uint32_t)src, (int)((src >> 32) & 0xffff),
-                      (int)(rem > 0x7fffffff ? 0x7fffffff : (rem > 0 ? rem : 0)), 0x00020000};
-    asm volatile("s_nop 4" ::: "memory");  // descriptor SGPRs -> buffer_load
+    const int4v rs = {(int)(uint32_t)src, (int)((src >> 32) & 0xffff), rsrc_size<true>(rem),
+                      0x00020000};
+    rsrc_hazard_nop();
     if constexpr (inb) {
 #pragma unroll
       for (int k = 0; k < G::IPT; ++k)
@@ -791,9 +737,9 @@ __global__ __launch_bounds__(NW * 64, (NPL == 1 || NW == 4) ? 2 : 1) void k_conv
       const uint64_t xsrc = reinterpret_cast<uint64_t>(p.sx + (int64_t)n * Cx * cT);
       const int64_t xbytes = (int64_t)Cx * cT * 4;
       const int4v rsx = {(int)(uint32_t)xsrc, (int)((xsrc >> 32) & 0xffff),
-                         (int)(xbytes > 0x7fffffff ? 0x7fffffff : xbytes), 0x00020000};
+                         rsrc_size(xbytes), 0x00020000};
       const int nvf = min(G::FT, p.M - m0);
-      asm volatile("s_nop 4" ::: "memory");  // descriptor SGPRs -> buffer_load
+      rsrc_hazard_nop();
 #pragma unroll
       for (int e = 0; e < 32; ++e)
         if (e >= e0 && e < e1) {
@@ -824,10 +770,10 @@ __global__ __launch_bounds__(NW * 64, (NPL == 1 || NW == 4) ? 2 : 1) void k_conv
           h.z = u(4) | (u(5) << 16);
           h.w = u(6) | (u(7) << 16);
         } else {
-          h.x = pk2(sx[k][0], sx[k][1]);
-          h.y = pk2(sx[k][2], sx[k][3]);
-          h.z = pk2(sx[k][4], sx[k][5]);
-          h.w = pk2(sx[k][6], sx[k][7]);
+          h.x = pk_bf16(sx[k][0], sx[k][1]);
+          h.y = pk_bf16(sx[k][2], sx[k][3]);
+          h.z = pk_bf16(sx[k][4], sx[k][5]);
+          h.w = pk_bf16(sx[k][6], sx[k][7]);
         }
         *reinterpret_cast<uint4 *>(win + loff[k]) = h;
       } else if (NPL == 2 && loff[k] >= 0) {  // fp16 (h, l) planes of the scaled input
@@ -860,10 +806,10 @@ __global__ __launch_bounds__(NW * 64, (NPL == 1 || NW == 4) ? 2 : 1) void k_conv
         *reinterpret_cast<uint4 *>(win + loff[k] + 32) = l;
       } else if (loff[k] >= 0) {
         uint4 h, m, l;
-        split2(sx[k][0], sx[k][1], h.x, m.x, l.x);
-        split2(sx[k][2], sx[k][3], h.y, m.y, l.y);
-        split2(sx[k][4], sx[k][5], h.z, m.z, l.z);
-        split2(sx[k][6], sx[k][7], h.w, m.w, l.w);
+        split_bf16x3(sx[k][0], sx[k][1], h.x, m.x, l.x);
+        split_bf16x3(sx[k][2], sx[k][3], h.y, m.y, l.y);
+        split_bf16x3(sx[k][4], sx[k][5], h.z, m.z, l.z);
+        split_bf16x3(sx[k][6], sx[k][7], h.w, m.w, l.w);
         *reinterpret_cast<uint4 *>(win + loff[k]) = h;
         *reinterpret_cast<uint4 *>(win + loff[k] + 32) = m;
         *reinterpret_cast<uint4 *>(win + loff[k] + 64) = l;
@@ -885,13 +831,7 @@ __global__ __launch_bounds__(NW * 64, (NPL == 1 || NW == 4) ? 2 : 1) void k_conv
       if (d < G::WDMA && (qq < 0 || i % TG == qq)) {
         const unsigned voffw = (unsigned)(step * G::WST + d * 1024 + lane * 16);
         const unsigned m0v = lds0 + (unsigned)(buf * G::WST + d * 1024);
-        unsigned keep;
-        asm volatile(
-            "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\t"
-            "buffer_load_dwordx4 %2, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
-            : "=&s"(keep)
-            : "s"(m0v), "v"(voffw), "s"(rsw)
-            : "memory");
+        lds_dma_b128(rsw, voffw, m0v);
       }
     }
   };
@@ -916,21 +856,21 @@ __global__ __launch_bounds__(NW * 64, (NPL == 1 || NW == 4) ? 2 : 1) void k_conv
     for (int i = 0; i < 16; ++i) acl[j][i] = 0.f;
 
   struct Frag {
-    bf16x8_t a[NPL][MR], b[NPL][2];
+    bf16x8 a[NPL][MR], b[NPL][2];
   };
   auto ld = [&](const char *wa, const char *win, int qq, int q, Frag &f) {
 #pragma unroll
     for (int pl = 0; pl < NPL; ++pl)
 #pragma unroll
       for (int rb = 0; rb < MR; ++rb)
-        f.a[pl][rb] = *reinterpret_cast<const bf16x8_t *>(
+        f.a[pl][rb] = *reinterpret_cast<const bf16x8 *>(
             wa + (pl * TG + qq) * 2 * G::ROWS * 16 + rb * 32 * 16);
 #pragma unroll
     for (int pl = 0; pl < NPL; ++pl)
 #pragma unroll
       for (int j = 0; j < 2; ++j)
         f.b[pl][j] =
-            *reinterpret_cast<const bf16x8_t *>(win + bo[j] + (q * G::FP + 2 * pl) * 16);
+            *reinterpret_cast<const bf16x8 *>(win + bo[j] + (q * G::FP + 2 * pl) * 16);
   };
   // the six products (plane of A, plane of B) of one tap over the MR x 2 tiles
   // (NPL = 1: the one product)
@@ -1009,13 +949,13 @@ __global__ __launch_bounds__(NW * 64, (NPL == 1 || NW == 4) ? 2 : 1) void k_conv
   auto lda = [&](const char *wl, int qq, int pl) {
 #pragma unroll
     for (int rb = 0; rb < MR; ++rb)
-      f[0].a[pl][rb] = *reinterpret_cast<const bf16x8_t *>(
+      f[0].a[pl][rb] = *reinterpret_cast<const bf16x8 *>(
           wl + (pl * TG + qq) * 2 * G::ROWS * 16 + rb * 32 * 16);
   };
   auto ldb = [&](const char *wn, int q, int pl) {
 #pragma unroll
     for (int j = 0; j < 2; ++j)
-      f[0].b[pl][j] = *reinterpret_cast<const bf16x8_t *>(wn + bo[j] + (q * G::FP + 2 * pl) * 16);
+      f[0].b[pl][j] = *reinterpret_cast<const bf16x8 *>(wn + bo[j] + (q * G::FP + 2 * pl) * 16);
   };
   auto tap2 = [&](bool nx, const char *wl, const char *wn, int ql, int qn) {
     if constexpr (NPL == 2) {
@@ -1074,7 +1014,7 @@ __global__ __launch_bounds__(NW * 64, (NPL == 1 || NW == 4) ? 2 : 1) void k_conv
         asm volatile("s_waitcnt vmcnt(%0)" ::"n"(G::wait_n(g)) : "memory");
       else  // a tile's last steps: fewer weight steps were issued after DMA(s)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+      wait_lgkm_barrier();
       const char *wa = wbuf0 + (s % G::NWB) * G::WST + ao;
       ld(wa, win, 0, g * TG, f[0]);  // tap 0's fragment reads
       // (VMEM issue after this step's first fragment reads: a compiler wait
@@ -1108,7 +1048,7 @@ __global__ __launch_bounds__(NW * 64, (NPL == 1 || NW == 4) ? 2 : 1) void k_conv
         // issued after the loads (step g = 0): the weight pieces of steps 1..NG-1
         wait_img<(G::NG - 1) * G::DPWMIN>(st);
         if (G::NWIN == 1)  // single window: every wave is done reading chunk c's
-          asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+          wait_lgkm_barrier();
         write_img(win0 + (G::NWIN == 2 ? ((c + 1) & 1) * G::IMG : 0), c + 1, st);
       }
     }
@@ -1301,7 +1241,7 @@ __global__ __launch_bounds__(256) void k_pack_conv_w_x3_multi(PackJobs js) {
       unsigned w4[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const bf16x2_t pr = {pv[pl][2 * i], pv[pl][2 * i + 1]};
+        const bf16x2 pr = {pv[pl][2 * i], pv[pl][2 * i + 1]};
         w4[i] = __builtin_bit_cast(unsigned, pr);
       }
       *reinterpret_cast<uint4 *>(out + base + pl * pstride) = make_uint4(w4[0], w4[1], w4[2], w4[3]);
@@ -1781,8 +1721,8 @@ __global__ __launch_bounds__(512, 1) void k_wgrad_x3(WgradParams p) {
       *reinterpret_cast<uint2 *>(dst + pl) = l;
     } else {
       uint2 h, m, l;
-      split2(xv[0], xv[1], h.x, m.x, l.x);
-      split2(xv[2], xv[3], h.y, m.y, l.y);
+      split_bf16x3(xv[0], xv[1], h.x, m.x, l.x);
+      split_bf16x3(xv[2], xv[3], h.y, m.y, l.y);
       *reinterpret_cast<uint2 *>(dst) = h;
       *reinterpret_cast<uint2 *>(dst + pl) = m;
       *reinterpret_cast<uint2 *>(dst + 2 * pl) = l;
@@ -1893,7 +1833,7 @@ __global__ __launch_bounds__(512, 1) void k_wgrad_x3(WgradParams p) {
           for (int i = 0; i < 16; ++i) acm[mb][t][i] = 0.f;
     }
     struct Frag {
-      bf16x8_t a[MR][NPL], b[NPL][NT];
+      bf16x8 a[MR][NPL], b[NPL][NT];
     };
     // B lane bases of the current item (elements, plane 0): base ci = G::bidx(frame
     // of the lane half, tap of the group) holds window frame G::bframe(ci, q0, hi)
@@ -1907,13 +1847,13 @@ __global__ __launch_bounds__(512, 1) void k_wgrad_x3(WgradParams p) {
       for (int pl = 0; pl < NPL; ++pl) {
 #pragma unroll
         for (int mb = 0; mb < MR; ++mb)
-          f.a[mb][pl] = *reinterpret_cast<const bf16x8_t *>(P + pl * (G::PPL / 2) + mb * 64 * G::PPITCH);
+          f.a[mb][pl] = *reinterpret_cast<const bf16x8 *>(P + pl * (G::PPL / 2) + mb * 64 * G::PPITCH);
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
           const __bf16 *Qa = Q + qbs[G::bidx(ga / G::G4, t)] + pl * (G::QPL / 2) + (ga % G::G4) * 4;
           const __bf16 *Qb = Q + qbs[G::bidx(gb / G::G4, t)] + pl * (G::QPL / 2) + (gb % G::G4) * 4;
-          const bf16x4_t b0 = *reinterpret_cast<const bf16x4_t *>(Qa);
-          const bf16x4_t b1 = *reinterpret_cast<const bf16x4_t *>(Qb);
+          const bf16x4 b0 = *reinterpret_cast<const bf16x4 *>(Qa);
+          const bf16x4 b1 = *reinterpret_cast<const bf16x4 *>(Qb);
           f.b[pl][t] = __builtin_shufflevector(b0, b1, 0, 1, 2, 3, 4, 5, 6, 7);
         }
       }
@@ -1938,11 +1878,11 @@ __global__ __launch_bounds__(512, 1) void k_wgrad_x3(WgradParams p) {
       for (int t = 0; t < NT; ++t) acl[t] = mfma_p<NPL>(f.a[0][1], f.b[0][t], acl[t]);
       if constexpr (NPL == 3) {
 #pragma unroll
-        for (int t = 0; t < NT; ++t) acl[t] = mfma_x(f.a[0][0], f.b[2 % NPL][t], acl[t]);
+        for (int t = 0; t < NT; ++t) acl[t] = mfma_bf16(f.a[0][0], f.b[2 % NPL][t], acl[t]);
 #pragma unroll
-        for (int t = 0; t < NT; ++t) acl[t] = mfma_x(f.a[0][1], f.b[1][t], acl[t]);
+        for (int t = 0; t < NT; ++t) acl[t] = mfma_bf16(f.a[0][1], f.b[1][t], acl[t]);
 #pragma unroll
-        for (int t = 0; t < NT; ++t) acl[t] = mfma_x(f.a[0][2 % NPL], f.b[0][t], acl[t]);
+        for (int t = 0; t < NT; ++t) acl[t] = mfma_bf16(f.a[0][2 % NPL], f.b[0][t], acl[t]);
       }
     };
     Frag f[2];

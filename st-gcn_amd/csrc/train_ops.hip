@@ -251,7 +251,7 @@ __global__ __launch_bounds__(256) void k_head_pool(const float *y, float *pooled
 
 // ABI 9: the same mean over y = ReLU(BN2(U)) formed on load from the last
 // block's pre-BN2 tensor U (its y is never written): the element arithmetic of
-// k_bn_relu_fwd (kernels.hip bn_relu_fwd_body), the summation order of
+// k_bn_relu_fwd (kernels_bn.hip bn_relu_fwd_body), the summation order of
 // k_head_pool, so pooled is bit-identical to pooling the written y
 __global__ __launch_bounds__(256) void k_head_pool_u(const float *U, const float *mean,
                                                      const float *invstd, const float *g,

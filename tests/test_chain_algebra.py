@@ -1,5 +1,5 @@
 """CPU check of the deferred-dx chain's algebra (ABI 5; capi.hip, k_chain_coef
-in kernels.hip): block i's BN1 backward apply folded into block i-1's
+in kernels_bn.hip): block i's BN1 backward apply folded into block i-1's
 ReLU+BN2 backward needs block i-1's sums  sum m*dx  and  sum m*dx*uhat  BEFORE
 dx exists. The kernel forms them from the prev-mode sums of the spatial
 backward (s1 = sum m*dxhat, s2 = sum m*dxhat*uhat) and block i-1's forward
