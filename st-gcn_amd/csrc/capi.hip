@@ -21,25 +21,18 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <initializer_list>
 #include <string>
 #include <vector>
 
 #include "../../include/stgcn_hip.h"
+#include "host_common.h"
 #include "internal.h"
 #include "block_plan.h"
 
 using namespace stgcn;
 
 namespace {
-
 thread_local std::string g_err;
-
-int fail(int code, const std::string &msg) {
-  g_err = msg;
-  return code;
-}
-
 }  // namespace
 
 namespace stgcn {
@@ -48,30 +41,10 @@ void set_last_error(const std::string &msg) { g_err = msg; }
 
 namespace {
 
-#define HIP_TRY(expr)                                                                      \
-  do {                                                                                     \
-    hipError_t e_ = (expr);                                                                \
-    if (e_ != hipSuccess)                                                                  \
-      return fail(STGCN_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));        \
-  } while (0)
 // a stage of an entry point: its status ends the call
 #define STAGE(expr) \
   do { if (int rc_ = (expr)) return rc_; } while (0)
 
-// The alignment contract of stgcn_hip.h (Conventions): the first pointer of the
-// list that is off `align` bytes fails the call, by name, before any launch.
-// Null pointers pass (optional arguments; the null checks come first).
-struct NamedPtr {
-  const void *p;
-  const char *name;
-};
-int check_aligned(std::initializer_list<NamedPtr> ptrs, unsigned align) {
-  for (const NamedPtr &q : ptrs)
-    if (((uintptr_t)q.p & (align - 1)) != 0)
-      return fail(STGCN_E_INVALID,
-                  std::string(q.name) + ": must be " + std::to_string(align) + "-byte aligned");
-  return STGCN_OK;
-}
 #define STGCN_P(s, m) NamedPtr{(s)->m, #m}
 
 // bytes of a y_stats / x_stats block (ABI 7): 5 * C doubles of sums, then the

@@ -17,36 +17,17 @@
 // status[] and reads nothing of src.
 #include <hip/hip_runtime.h>
 
-#include <initializer_list>
 #include <string>
 
 #include "../../include/stgcn_hip.h"
-
-namespace stgcn {
-void set_last_error(const std::string &msg);  // capi.hip (stgcn_last_error)
-}
+#include "host_common.h"
 
 namespace {
 
 constexpr int kStageThreads = 256;
 
-int fail(int code, const std::string &m) {
-  stgcn::set_last_error(m);
-  return code;
-}
-
-struct NamedPtr {
-  const void *p;
-  const char *name;
-};
-int check_aligned(std::initializer_list<NamedPtr> ptrs, unsigned align) {
-  for (const NamedPtr &q : ptrs)
-    if (((uintptr_t)q.p & (align - 1)) != 0)
-      return fail(STGCN_E_INVALID,
-                  std::string(q.name) + ": must be " + std::to_string(align) + "-byte aligned");
-  return STGCN_OK;
-}
-#define NP(v) NamedPtr{v, #v}
+using stgcn::check_aligned;
+using stgcn::fail;
 
 // One source point: CS adjacent elements at the element's own alignment (the
 // load is one dwordx2 / x3 / x4: global loads need dword alignment only).

@@ -1,36 +1,27 @@
-// STGCN_FEATURE_OPTIMIZERS (stgcn_opt_*): the Adam family with decoupled weight
-// decay (torch.optim.AdamW) and AMSGrad, gfx950 only. One launch per table with
-// train_ops.hip's chunking (k_adam: 2048 elements per 256-thread block, a binary
-// search of the chunk prefix sums for the block's tensor). The
-// arithmetic is stated in include/stgcn_hip.h and DESIGN.md §1; stgcn_adam_step
-// and its kernels (train_ops.hip) are not touched by anything here.
+// The optimizer step of the training-step layer, gfx950 only: multi-tensor Adam
+// (torch.optim.Adam, lightning_model.py:196-197) with decoupled weight decay
+// (torch.optim.AdamW) and AMSGrad, and the gradient norm of clip_grad_norm_.
+// ONE launch over every tensor of a table: 2048 elements per 256-thread block, a
+// binary search of the chunk prefix sums for the block's tensor. stgcn_adam_step
+// / _dev / _dev2 (tables of stgcn_adam_tensor_t) and stgcn_opt_step (tables of
+// stgcn_opt_tensor_t) launch the same kernel template. The arithmetic is stated
+// in include/stgcn_hip.h and DESIGN.md §1.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstring>
 #include <string>
+#include <type_traits>
 
 #include "../../include/stgcn_hip.h"
-
-namespace stgcn {
-void set_last_error(const std::string &msg);  // capi.hip (stgcn_last_error)
-}
+#include "host_common.h"
 
 namespace {
 
-int fail(int code, const std::string &m) {
-  stgcn::set_last_error(m);
-  return code;
-}
+using stgcn::check_aligned;
+using stgcn::fail;
+using stgcn::NamedPtr;
 
-int check_word(const void *p, const char *name, unsigned align) {
-  if (((uintptr_t)p & (align - 1)) != 0)
-    return fail(STGCN_E_INVALID,
-                std::string(name) + ": must be " + std::to_string(align) + "-byte aligned");
-  return STGCN_OK;
-}
-
-constexpr int kChunk = 2048;  // elements per block (256 threads x 8), as kAdamChunk
+constexpr int kChunk = 2048;  // elements per block (256 threads x 8)
 
 // tensor of this block: the last t with chunk_start[t] <= blockIdx.x
 __device__ __forceinline__ int block_tensor(const int64_t *chunk_start, int ntensors) {
@@ -43,11 +34,46 @@ __device__ __forceinline__ int block_tensor(const int64_t *chunk_start, int nten
   return lo;
 }
 
+// A table (host or device copy): ntensors entries, then ntensors + 1 chunk
+// prefix sums
+template <typename T>
+size_t table_bytes(int ntensors) {
+  if (ntensors <= 0) return 0;
+  return (size_t)ntensors * sizeof(T) + (size_t)(ntensors + 1) * sizeof(int64_t);
+}
+template <typename T>
+const int64_t *chunk_starts(const void *table, int ntensors) {
+  return reinterpret_cast<const int64_t *>(reinterpret_cast<const T *>(table) + ntensors);
+}
+
+// The pointers of one table entry, whichever its type
+struct Entry {
+  float *param;
+  const float *grad;
+  float *m, *v, *vmax;  // exp_avg, exp_avg_sq, max_exp_avg_sq (AMSGrad)
+  int64_t numel;
+};
+__device__ __forceinline__ Entry entry(const stgcn_adam_tensor_t &t) {
+  return {t.param, t.grad, t.exp_avg, t.exp_avg_sq, nullptr, t.numel};
+}
+__device__ __forceinline__ Entry entry(const stgcn_opt_tensor_t &t) {
+  return {t.param, t.grad, t.s0, t.s1, t.s2, t.numel};
+}
+
 // ---------------------------------------------------------------------------
-// Adam family: adam_block's arithmetic (train_ops.hip) with the decoupled decay
-// ahead of the moment updates and the AMSGrad maximum. The scalars are formed
-// from doubles and rounded to float, on the host for a host step count and a
-// by-value lr, else by thread 0 of every block (the same expressions).
+// Adam. Per element, in fp32, in torch's order (optim/adam.py _multi_tensor_adam /
+// _single_tensor_adam), every operation rounded on its own:
+//   g  = grad * coef                    (COEF: the clip coefficient)
+//   g  = g + wd * p                     (wd != 0, not decoupled)
+//   p  = p * decay                      (decoupled: 1 - lr * wd; else 1: exact)
+//   m  = lerp(m, g, 1 - beta1)          (m + w (g - m) for w < 0.5)
+//   v  = v * beta2;  v = v + ((1 - beta2) * g) * g
+//   vd = vmax = max(vmax, v)            (AMS; else vd = v)
+//   p  = p + (-lr / bc1) * (m / (sqrt(vd) / sqrt(bc2) + eps))
+// with bc1 = 1 - beta1^step, bc2 = 1 - beta2^step. The scalars are formed from
+// doubles and rounded to float like torch's scalar arguments, on the host for a
+// host step count and a by-value lr, else by thread 0 of every block (the same
+// expressions).
 // ---------------------------------------------------------------------------
 struct AdamScalars {
   float lerp_w, beta2, one_minus_beta2, neg_step_size, bc2_sqrt, eps, wd, decay;
@@ -70,19 +96,21 @@ __host__ __device__ inline AdamScalars adam_scalars(double t, double lr, double 
   return sc;
 }
 
+// One step in any launch form (launch_adam fills host)
 struct AdamArgs {
   AdamScalars host;  // used when neither step_dev nor lr_dev is given
   double lr, beta1, beta2, eps, wd, step;
-  const float *step_dev, *lr_dev, *coef;
+  float *step_dev;             // the device step count, advanced by the call, or null
+  const float *lr_dev, *coef;  // device words read when the kernel runs, or null
   int decoupled;
 };
 
-__global__ void k_opt_tick(float *step) { *step = *step + 1.f; }
+__global__ void k_adam_tick(float *step) { *step = *step + 1.f; }
 
-template <bool AMS, bool COEF>
-__global__ __launch_bounds__(256) void k_opt_adam(const stgcn_opt_tensor_t *tab,
-                                                  const int64_t *chunk_start, int ntensors,
-                                                  AdamArgs a) {
+// T: stgcn_adam_tensor_t or stgcn_opt_tensor_t (the table's entry type)
+template <typename T, bool AMS, bool COEF>
+__global__ __launch_bounds__(256) void k_adam(const T *tab, const int64_t *chunk_start,
+                                              int ntensors, AdamArgs a) {
 #pragma clang fp contract(off)
   __shared__ AdamScalars sh;
   __shared__ float sh_coef;
@@ -99,59 +127,238 @@ __global__ __launch_bounds__(256) void k_opt_adam(const stgcn_opt_tensor_t *tab,
   const AdamScalars s = sh;
   const float coef = sh_coef;
   const int ti = block_tensor(chunk_start, ntensors);
-  const stgcn_opt_tensor_t t = tab[ti];
+  const Entry t = entry(tab[ti]);
   const int64_t base = ((int64_t)blockIdx.x - chunk_start[ti]) * kChunk;
   for (int i = threadIdx.x; i < kChunk; i += 256) {
     const int64_t e = base + i;
     if (e >= t.numel) break;
-    // (every operation rounded on its own, as in adam_block)
+    // (no fma contraction: as torch's unfused CPU loop rounds)
     float p = t.param[e];
     float g = t.grad[e];
     if constexpr (COEF) g = g * coef;
     if (s.wd != 0.f) g = g + s.wd * p;
     p = p * s.decay;  // (1 without decoupled decay: exact)
-    float m = t.s0[e];
+    float m = t.m[e];
     m = m + s.lerp_w * (g - m);
-    float v = t.s1[e] * s.beta2;
+    float v = t.v[e] * s.beta2;
     v = v + (s.one_minus_beta2 * g) * g;
     float vd = v;
     if constexpr (AMS) {
-      vd = fmaxf(t.s2[e], v);
-      t.s2[e] = vd;
+      vd = fmaxf(t.vmax[e], v);
+      t.vmax[e] = vd;
     }
     const float denom = sqrtf(vd) / s.bc2_sqrt + s.eps;
     p = p + s.neg_step_size * (m / denom);
-    t.s0[e] = m;
-    t.s1[e] = v;
+    t.m[e] = m;
+    t.v[e] = v;
     t.param[e] = p;
   }
 }
 
-const int64_t *chunk_starts(const void *dev_table, int ntensors) {
-  return reinterpret_cast<const int64_t *>(reinterpret_cast<const char *>(dev_table) +
-                                           (size_t)ntensors * sizeof(stgcn_opt_tensor_t));
-}
-
-int check_table_args(const void *dev_table, int ntensors, int64_t total_chunks) {
-  if (!dev_table || ntensors <= 0 || total_chunks <= 0 || total_chunks > INT32_MAX)
-    return fail(STGCN_E_INVALID, "opt: bad table / tensor count / chunk count");
-  return check_word(dev_table, "dev_table", 8);
-}
-
-template <bool AMS>
-void launch_adam(bool coef, unsigned grid, hipStream_t s, const stgcn_opt_tensor_t *tab,
-                 const int64_t *cs, int ntensors, const AdamArgs &a) {
-  if (coef)
-    hipLaunchKernelGGL((k_opt_adam<AMS, true>), dim3(grid), dim3(256), 0, s, tab, cs, ntensors,
-                       a);
+template <typename T, bool AMS>
+void launch_adam_kernel(unsigned grid, hipStream_t s, const void *dev_table, int ntensors,
+                        const AdamArgs &a) {
+  const T *tab = reinterpret_cast<const T *>(dev_table);
+  const int64_t *cs = chunk_starts<T>(dev_table, ntensors);
+  if (a.coef)
+    hipLaunchKernelGGL((k_adam<T, AMS, true>), dim3(grid), dim3(256), 0, s, tab, cs, ntensors, a);
   else
-    hipLaunchKernelGGL((k_opt_adam<AMS, false>), dim3(grid), dim3(256), 0, s, tab, cs, ntensors,
-                       a);
+    hipLaunchKernelGGL((k_adam<T, AMS, false>), dim3(grid), dim3(256), 0, s, tab, cs, ntensors, a);
+}
+
+// The launches of every Adam entry point, after its own argument checks: the
+// tick of a device step count, then the element kernel. The caller reads
+// hipGetLastError().
+template <typename T>
+void launch_adam(const void *dev_table, int ntensors, int64_t total_chunks, bool amsgrad,
+                 AdamArgs a, void *stream) {
+  hipStream_t s = (hipStream_t)stream;
+  a.host = AdamScalars{};
+  if (!a.step_dev && !a.lr_dev)
+    a.host = adam_scalars(a.step, a.lr, a.beta1, a.beta2, a.eps, a.wd, a.decoupled != 0);
+  if (a.step_dev) hipLaunchKernelGGL(k_adam_tick, dim3(1), dim3(1), 0, s, a.step_dev);
+  const unsigned grid = (unsigned)total_chunks;
+  if constexpr (std::is_same_v<T, stgcn_opt_tensor_t>) {  // (an Adam entry has no vmax slot)
+    if (amsgrad) return launch_adam_kernel<T, true>(grid, s, dev_table, ntensors, a);
+  }
+  launch_adam_kernel<T, false>(grid, s, dev_table, ntensors, a);
+}
+
+// the arguments of the legacy entry points (stgcn_adam_step / _dev / _dev2)
+AdamArgs legacy_args(double lr, double beta1, double beta2, double eps, double wd) {
+  AdamArgs a{};
+  a.lr = lr;
+  a.beta1 = beta1;
+  a.beta2 = beta2;
+  a.eps = eps;
+  a.wd = wd;
+  return a;
+}
+
+// A host table from the caller's entries: prep(i, entry) checks (and may amend)
+// each one; then the chunk prefix sums. who: the prefix of the error texts.
+template <typename T, typename Prep>
+int fill_table(const char *who, const T *tensors, int ntensors, void *host_table,
+               int64_t *total_chunks, Prep prep) {
+  T *tab = reinterpret_cast<T *>(host_table);
+  int64_t *cs = const_cast<int64_t *>(chunk_starts<T>(host_table, ntensors));
+  int64_t chunks = 0;
+  for (int i = 0; i < ntensors; ++i) {
+    T t = tensors[i];
+    if (int rc = prep(i, t)) return rc;
+    tab[i] = t;
+    cs[i] = chunks;
+    chunks += (t.numel + kChunk - 1) / kChunk;
+  }
+  cs[ntensors] = chunks;
+  if (chunks > INT32_MAX)
+    return fail(STGCN_E_UNSUPPORTED, std::string(who) + ": too many elements");
+  *total_chunks = chunks;
+  return STGCN_OK;
+}
+
+// Gradient norm over an Adam table (stgcn_grad_norm). k_grad_sq: block b = chunk
+// b of the table (k_adam's chunking), its sum of grad^2 in fp64 -- per
+// thread in element order, then the block in a fixed tree -- stored to
+// partials[b]. k_grad_norm: one workgroup adds the partials (thread i takes
+// i, i + 256, ... in order; the same tree) and writes the norm and the clip
+// coefficient. Plain stores only: the result does not depend on scheduling.
+__device__ __forceinline__ double block_sum_fixed(double v, double *red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) red[wave] = v;
+  __syncthreads();
+  return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+__global__ __launch_bounds__(256) void k_grad_sq(const stgcn_adam_tensor_t *tab,
+                                                 const int64_t *chunk_start, int ntensors,
+                                                 double *partials) {
+  __shared__ double red[4];
+  const int64_t b = blockIdx.x;
+  const int ti = block_tensor(chunk_start, ntensors);
+  const float *grad = tab[ti].grad;
+  const int64_t numel = tab[ti].numel;
+  const int64_t base = (b - chunk_start[ti]) * kChunk;
+  double s = 0.0;
+  for (int i = threadIdx.x; i < kChunk; i += 256) {
+    const int64_t e = base + i;
+    if (e >= numel) break;
+    const double g = (double)grad[e];
+    s += g * g;
+  }
+  s = block_sum_fixed(s, red);
+  if (threadIdx.x == 0) partials[b] = s;
+}
+
+__global__ __launch_bounds__(256) void k_grad_norm(const double *partials, int64_t n,
+                                                   float max_norm, float *norm_out,
+                                                   float *coef_out) {
+  __shared__ double red[4];
+  double s = 0.0;
+  for (int64_t i = threadIdx.x; i < n; i += 256) s += partials[i];
+  s = block_sum_fixed(s, red);
+  if (threadIdx.x == 0) {
+    const float norm = (float)sqrt(s);
+    *norm_out = norm;
+    *coef_out = fminf(1.f, max_norm / (norm + 1e-6f));
+  }
 }
 
 }  // namespace
 
 extern "C" {
+
+size_t stgcn_adam_table_bytes(int ntensors) { return table_bytes<stgcn_adam_tensor_t>(ntensors); }
+
+int stgcn_adam_build_table(const stgcn_adam_tensor_t *tensors, int ntensors, void *host_table,
+                           size_t table_bytes, int64_t *total_chunks) {
+  if (!tensors || ntensors <= 0 || !host_table || !total_chunks)
+    return fail(STGCN_E_INVALID, "adam: null argument or no tensors");
+  if (table_bytes < stgcn_adam_table_bytes(ntensors))
+    return fail(STGCN_E_INVALID, "adam: table buffer too small");
+  return fill_table("adam", tensors, ntensors, host_table, total_chunks,
+                    [](int i, stgcn_adam_tensor_t &t) {
+    if (!t.param || !t.grad || !t.exp_avg || !t.exp_avg_sq || t.numel <= 0)
+      return fail(STGCN_E_INVALID,
+                  "adam: tensor " + std::to_string(i) + " has a null pointer or numel <= 0");
+    if ((((uintptr_t)t.param | (uintptr_t)t.grad | (uintptr_t)t.exp_avg |
+          (uintptr_t)t.exp_avg_sq) & 3) != 0)
+      return fail(STGCN_E_INVALID,
+                  "adam: tensor " + std::to_string(i) + ": param / grad / exp_avg / exp_avg_sq "
+                  "must be 4-byte aligned");
+    return (int)STGCN_OK;
+  });
+}
+
+int stgcn_adam_step(const void *dev_table, int ntensors, int64_t total_chunks, double lr,
+                    double beta1, double beta2, double eps, double weight_decay, int64_t step,
+                    void *stream) {
+  if (!dev_table || ntensors <= 0 || total_chunks <= 0 || step <= 0)
+    return fail(STGCN_E_INVALID, "adam: bad table / chunk count / step");
+  if (int rc = check_aligned({NP(dev_table)}, 8)) return rc;
+  AdamArgs a = legacy_args(lr, beta1, beta2, eps, weight_decay);
+  a.step = (double)step;
+  launch_adam<stgcn_adam_tensor_t>(dev_table, ntensors, total_chunks, false, a, stream);
+  HIP_TRY(hipGetLastError());
+  return STGCN_OK;
+}
+
+int stgcn_adam_step_dev(const void *dev_table, int ntensors, int64_t total_chunks, double lr,
+                        double beta1, double beta2, double eps, double weight_decay, float *step,
+                        void *stream) {
+  if (!dev_table || ntensors <= 0 || total_chunks <= 0 || !step)
+    return fail(STGCN_E_INVALID, "adam: bad table / chunk count / step pointer");
+  if (int rc = check_aligned({NP(dev_table)}, 8)) return rc;
+  if (int rc = check_aligned({NP(step)}, 4)) return rc;
+  AdamArgs a = legacy_args(lr, beta1, beta2, eps, weight_decay);
+  a.step_dev = step;
+  launch_adam<stgcn_adam_tensor_t>(dev_table, ntensors, total_chunks, false, a, stream);
+  HIP_TRY(hipGetLastError());
+  return STGCN_OK;
+}
+
+int stgcn_adam_step_dev2(const void *dev_table, int ntensors, int64_t total_chunks,
+                         const float *lr_dev, const float *grad_coef, double beta1, double beta2,
+                         double eps, double weight_decay, float *step, void *stream) {
+  if (!dev_table || ntensors <= 0 || total_chunks <= 0 || !step)
+    return fail(STGCN_E_INVALID, "adam: bad table / chunk count / step pointer");
+  if (!lr_dev) return fail(STGCN_E_INVALID, "adam: lr_dev is null");
+  if (int rc = check_aligned({NP(dev_table)}, 8)) return rc;
+  if (int rc = check_aligned({NP(step), NP(lr_dev), NP(grad_coef)}, 4)) return rc;
+  AdamArgs a = legacy_args(0.0, beta1, beta2, eps, weight_decay);
+  a.step_dev = step;
+  a.lr_dev = lr_dev;
+  a.coef = grad_coef;
+  launch_adam<stgcn_adam_tensor_t>(dev_table, ntensors, total_chunks, false, a, stream);
+  HIP_TRY(hipGetLastError());
+  return STGCN_OK;
+}
+
+size_t stgcn_grad_norm_bytes(int64_t total_chunks) {
+  return total_chunks > 0 ? (size_t)total_chunks * sizeof(double) : 0;
+}
+
+int stgcn_grad_norm(const void *dev_table, int ntensors, int64_t total_chunks, double max_norm,
+                    double *partials, float *norm_out, float *coef_out, void *stream) {
+  if (!dev_table || ntensors <= 0 || total_chunks <= 0 || total_chunks > INT32_MAX)
+    return fail(STGCN_E_INVALID, "grad_norm: bad table / chunk count");
+  if (!partials) return fail(STGCN_E_INVALID, "grad_norm: partials is null");
+  if (!norm_out) return fail(STGCN_E_INVALID, "grad_norm: norm_out is null");
+  if (!coef_out) return fail(STGCN_E_INVALID, "grad_norm: coef_out is null");
+  if (!(max_norm > 0.0)) return fail(STGCN_E_INVALID, "grad_norm: max_norm must be positive");
+  if (int rc = check_aligned({NP(dev_table), NP(partials)}, 8)) return rc;
+  if (int rc = check_aligned({NP(norm_out), NP(coef_out)}, 4)) return rc;
+  const auto *tab = reinterpret_cast<const stgcn_adam_tensor_t *>(dev_table);
+  hipLaunchKernelGGL(k_grad_sq, dim3((unsigned)total_chunks), dim3(256), 0, (hipStream_t)stream,
+                     tab, chunk_starts<stgcn_adam_tensor_t>(dev_table, ntensors), ntensors,
+                     partials);
+  hipLaunchKernelGGL(k_grad_norm, dim3(1), dim3(256), 0, (hipStream_t)stream, partials,
+                     total_chunks, (float)max_norm, norm_out, coef_out);
+  HIP_TRY(hipGetLastError());
+  return STGCN_OK;
+}
 
 int stgcn_opt_check(const stgcn_opt_desc_t *d) {
   if (!d) return fail(STGCN_E_INVALID, "opt: null descriptor");
@@ -170,16 +377,12 @@ int stgcn_opt_check(const stgcn_opt_desc_t *d) {
   if (!(d->eps >= 0.0)) return fail(STGCN_E_INVALID, "opt: eps must be >= 0");
   if (!d->step_dev && d->step < 1)
     return fail(STGCN_E_INVALID, "opt: step must be >= 1 (or step_dev given)");
-  if (int rc = check_word(d->lr_dev, "lr_dev", 4)) return rc;
-  if (int rc = check_word(d->grad_coef, "grad_coef", 4)) return rc;
-  if (int rc = check_word(d->step_dev, "step_dev", 4)) return rc;
-  return STGCN_OK;
+  return check_aligned({NamedPtr{d->lr_dev, "lr_dev"}, NamedPtr{d->grad_coef, "grad_coef"},
+                        NamedPtr{d->step_dev, "step_dev"}},
+                       4);
 }
 
-size_t stgcn_opt_table_bytes(int ntensors) {
-  if (ntensors <= 0) return 0;
-  return (size_t)ntensors * sizeof(stgcn_opt_tensor_t) + (size_t)(ntensors + 1) * sizeof(int64_t);
-}
+size_t stgcn_opt_table_bytes(int ntensors) { return table_bytes<stgcn_opt_tensor_t>(ntensors); }
 
 int stgcn_opt_build_table(const stgcn_opt_desc_t *d, const stgcn_opt_tensor_t *tensors,
                           int ntensors, void *host_table, size_t table_bytes,
@@ -190,12 +393,8 @@ int stgcn_opt_build_table(const stgcn_opt_desc_t *d, const stgcn_opt_tensor_t *t
   if (table_bytes < stgcn_opt_table_bytes(ntensors))
     return fail(STGCN_E_INVALID, "opt: table buffer too small");
   const bool need[3] = {true, true, (d->flags & STGCN_OPT_AMSGRAD) != 0};
-  auto *tab = reinterpret_cast<stgcn_opt_tensor_t *>(host_table);
-  auto *cs = reinterpret_cast<int64_t *>(reinterpret_cast<char *>(host_table) +
-                                         (size_t)ntensors * sizeof(stgcn_opt_tensor_t));
-  int64_t chunks = 0;
-  for (int i = 0; i < ntensors; ++i) {
-    const stgcn_opt_tensor_t &t = tensors[i];
+  return fill_table("opt", tensors, ntensors, host_table, total_chunks,
+                    [&need](int i, stgcn_opt_tensor_t &t) {
     const std::string who = "opt: tensor " + std::to_string(i);
     if (!t.param || !t.grad) return fail(STGCN_E_INVALID, who + ": param or grad is null");
     if (t.numel <= 0) return fail(STGCN_E_INVALID, who + ": numel <= 0");
@@ -208,28 +407,18 @@ int stgcn_opt_build_table(const stgcn_opt_desc_t *d, const stgcn_opt_tensor_t *t
     if ((((uintptr_t)t.param | (uintptr_t)t.grad | (uintptr_t)t.s0 | (uintptr_t)t.s1 |
           (uintptr_t)t.s2) & 3) != 0)
       return fail(STGCN_E_INVALID, who + ": param / grad / s0 / s1 / s2 must be 4-byte aligned");
-    tab[i] = t;
-    tab[i].reserved = 0;
-    cs[i] = chunks;
-    chunks += (t.numel + kChunk - 1) / kChunk;
-  }
-  cs[ntensors] = chunks;
-  if (chunks > INT32_MAX) return fail(STGCN_E_UNSUPPORTED, "opt: too many elements");
-  *total_chunks = chunks;
-  return STGCN_OK;
+    t.reserved = 0;
+    return (int)STGCN_OK;
+  });
 }
 
 int stgcn_opt_step(const stgcn_opt_desc_t *d, const void *dev_table, int ntensors,
                    int64_t total_chunks, void *stream) {
   if (int rc = stgcn_opt_check(d)) return rc;
-  if (int rc = check_table_args(dev_table, ntensors, total_chunks)) return rc;
-  const auto *tab = reinterpret_cast<const stgcn_opt_tensor_t *>(dev_table);
-  const int64_t *cs = chunk_starts(dev_table, ntensors);
-  const unsigned grid = (unsigned)total_chunks;
-  hipStream_t s = (hipStream_t)stream;
-  const bool coef = d->grad_coef != nullptr;
-  const bool decoupled = (d->flags & STGCN_OPT_DECOUPLED_WD) != 0;
-  AdamArgs a;
+  if (!dev_table || ntensors <= 0 || total_chunks <= 0 || total_chunks > INT32_MAX)
+    return fail(STGCN_E_INVALID, "opt: bad table / tensor count / chunk count");
+  if (int rc = check_aligned({NP(dev_table)}, 8)) return rc;
+  AdamArgs a{};
   a.lr = d->lr;
   a.beta1 = d->beta1;
   a.beta2 = d->beta2;
@@ -239,15 +428,9 @@ int stgcn_opt_step(const stgcn_opt_desc_t *d, const void *dev_table, int ntensor
   a.step_dev = d->step_dev;
   a.lr_dev = d->lr_dev;
   a.coef = d->grad_coef;
-  a.decoupled = decoupled;
-  std::memset(&a.host, 0, sizeof(a.host));
-  if (!d->step_dev && !d->lr_dev)
-    a.host = adam_scalars(a.step, a.lr, a.beta1, a.beta2, a.eps, a.wd, decoupled);
-  if (d->step_dev) hipLaunchKernelGGL(k_opt_tick, dim3(1), dim3(1), 0, s, d->step_dev);
-  if (d->flags & STGCN_OPT_AMSGRAD)
-    launch_adam<true>(coef, grid, s, tab, cs, ntensors, a);
-  else
-    launch_adam<false>(coef, grid, s, tab, cs, ntensors, a);
+  a.decoupled = (d->flags & STGCN_OPT_DECOUPLED_WD) != 0;
+  launch_adam<stgcn_opt_tensor_t>(dev_table, ntensors, total_chunks,
+                                  (d->flags & STGCN_OPT_AMSGRAD) != 0, a, stream);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(STGCN_E_HIP, std::string("opt: ") + hipGetErrorString(e));
   return STGCN_OK;

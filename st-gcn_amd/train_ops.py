@@ -180,7 +180,7 @@ def _loss_options(weight, label_smoothing, classes, dev):
 
 def head_eval(y, W, b, labels, topk=1, metrics=None, from_u=None, weight=None,
               label_smoothing=0.0):
-    """The head of an evaluation step (stgcn_head_eval / stgcn_head_eval_u): y
+    """The head of an evaluation step (stgcn_head_eval_loss / _u): y
     (N, C, T, V), W (classes, C), b (classes), labels int64 (N) -> (loss, logits
     (N, classes), pred int32 (N), lossv (N) the per-clip losses), with ``StgcnHeadFn``'s logits and loss bit for
     bit when every label is valid; a label outside [0, classes) is ignored as
@@ -188,9 +188,10 @@ def head_eval(y, W, b, labels, topk=1, metrics=None, from_u=None, weight=None,
     batch (its topk then applies). from_u = (U, stats2, g2, b2): y is None and the
     pool forms ReLU(BN2(U)) on load. No autograd, no host read.
     weight (contiguous float32 GPU tensor, one element per class, on y's device)
-    / label_smoothing: F.cross_entropy's, through stgcn_head_eval_loss: loss is
-    the sum of the per-clip losses over D = the valid clips' summed w[label],
-    and 0 (torch: NaN) when D == 0. With neither, the call is stgcn_head_eval."""
+    / label_smoothing: F.cross_entropy's: loss is the sum of the per-clip losses
+    over D = the valid clips' summed w[label], and 0 (torch: NaN) when D == 0.
+    Every call goes through stgcn_head_eval_loss / _u (without options: flags 0,
+    eps 0, which has stgcn_head_eval's bits)."""
     lib = hip_lib.lib()
     src = y if from_u is None else from_u[0]
     if from_u is None:
@@ -212,41 +213,27 @@ def head_eval(y, W, b, labels, topk=1, metrics=None, from_u=None, weight=None,
         topk, mbuf = metrics.topk, metrics.buf
     dev = src.device
     eps = _loss_options(weight, label_smoothing, classes, dev)
-    options = weight is not None or eps != 0.0
-    if options:
-        d = hip_lib.LossDesc(N, C, L, classes, int(topk),
-                             hip_lib.LOSS_WEIGHT if weight is not None else 0, eps)
-        hip_lib.check(lib.stgcn_loss_check(ctypes.byref(d)))
-        denom = torch.empty((), device=dev, dtype=torch.float32)
-    else:
-        d = hip_lib.EvalDesc(N, C, L, classes, int(topk))
+    d = hip_lib.LossDesc(N, C, L, classes, int(topk),
+                         hip_lib.LOSS_WEIGHT if weight is not None else 0, eps)
+    hip_lib.check(lib.stgcn_loss_check(ctypes.byref(d)))
     pooled = torch.empty((N, C), device=dev, dtype=torch.float32)
     logits = torch.empty((N, classes), device=dev, dtype=torch.float32)
     lossv = torch.empty(N, device=dev, dtype=torch.float32)
+    denom = torch.empty((), device=dev, dtype=torch.float32)
     loss = torch.empty((), device=dev, dtype=torch.float32)
     pred = torch.empty(N, device=dev, dtype=torch.int32)
+    rest = (W, b, weight, labels, pooled, logits, lossv, denom, loss, pred, mbuf)
     if from_u is not None:
         U, stats2, g2, b2 = from_u
         for t, n in ((stats2, "stats2"), (g2, "g2"), (b2, "b2")):
             _check_f32(t, n)
         if stats2.numel() < 2 * C or g2.numel() != C or b2.numel() != C:
             raise RuntimeError("head: BN2 parameters do not match U")
-        if options:
-            hip_lib.check(lib.stgcn_head_eval_loss_u(ctypes.byref(d), *[hip_lib.ptr(t) for t in (
-                U, stats2, g2, b2, W, b, weight, labels, pooled, logits, lossv, denom, loss, pred,
-                mbuf)], hip_lib.stream_handle(dev)))
-        else:
-            hip_lib.check(lib.stgcn_head_eval_u(ctypes.byref(d), *[hip_lib.ptr(t) for t in (
-                U, stats2, g2, b2, W, b, labels, pooled, logits, lossv, loss, pred, mbuf)],
-                hip_lib.stream_handle(dev)))
-    elif options:
-        hip_lib.check(lib.stgcn_head_eval_loss(ctypes.byref(d), *[hip_lib.ptr(t) for t in (
-            src, W, b, weight, labels, pooled, logits, lossv, denom, loss, pred, mbuf)],
-            hip_lib.stream_handle(dev)))
+        hip_lib.check(lib.stgcn_head_eval_loss_u(ctypes.byref(d), *[hip_lib.ptr(t) for t in (
+            U, stats2, g2, b2) + rest], hip_lib.stream_handle(dev)))
     else:
-        hip_lib.check(lib.stgcn_head_eval(ctypes.byref(d), *[hip_lib.ptr(t) for t in (
-            src, W, b, labels, pooled, logits, lossv, loss, pred, mbuf)],
-            hip_lib.stream_handle(dev)))
+        hip_lib.check(lib.stgcn_head_eval_loss(ctypes.byref(d), *[hip_lib.ptr(t) for t in (
+            src,) + rest], hip_lib.stream_handle(dev)))
     return loss, logits, pred, lossv
 
 
@@ -260,15 +247,15 @@ class FusedAdam(torch.optim.Optimizer):
 
     capturable=True (as torch.optim.Adam(capturable=True)): the step count lives
     on the device (one float tensor per group, shared by the group's parameters'
-    ``state["step"]``) and is advanced by the library (stgcn_adam_step_dev, ABI
-    11), so ``step()`` reads nothing from the device and can be captured in a HIP
+    ``state["step"]``) and is advanced by the library (stgcn_opt_step's
+    step_dev), so ``step()`` reads nothing from the device and can be captured in a HIP
     graph (``GraphedStep``). A table built during a capture (the captured
     backward allocates new gradients) is written into a pinned buffer set aside
     by the last eager build and kept alive with the table: every replay's copy
     re-reads it.
 
     lr as a tensor (capturable=True only): a 0-dim float32 tensor on the
-    parameters' device is read by the kernel when it runs (stgcn_adam_step_dev2),
+    parameters' device is read by the kernel when it runs (stgcn_opt_step's lr_dev),
     so a scheduler that writes it with ``fill_`` between replays (torch's
     lr_scheduler does for a tensor lr) takes effect without a re-capture. Any
     other tensor raises; a float lr takes the by-value call as before.
@@ -284,11 +271,12 @@ class FusedAdam(torch.optim.Optimizer):
     gradients after the step sees the unclipped ones. Under data parallelism the
     step runs after the all-reduce, so the norm is the global one.
 
-    amsgrad / decoupled_weight_decay (per group, as torch.optim.Adam's): a group
-    with either takes stgcn_opt_step -- the same arithmetic with p = p * (1 - lr *
-    wd) in place of the gradient's decay term (torch.optim.AdamW) and / or the
-    running maximum ``max_exp_avg_sq`` in the denominator -- in every launch form
-    above. A group with neither takes the calls it always took."""
+    amsgrad / decoupled_weight_decay (per group, as torch.optim.Adam's): the same
+    arithmetic with p = p * (1 - lr * wd) in place of the gradient's decay term
+    (torch.optim.AdamW) and / or the running maximum ``max_exp_avg_sq`` in the
+    denominator, in every launch form above. Every group steps through
+    stgcn_opt_step, whose stgcn_opt_check refuses a negative lr / eps /
+    weight_decay and betas outside [0, 1) (as torch.optim.Adam's constructor)."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0,
                  amsgrad=False, capturable=False, max_grad_norm=None,
@@ -347,110 +335,57 @@ class FusedAdam(torch.optim.Optimizer):
                     raise RuntimeError("FusedAdam: parameters of a group at different steps")
                 step = steps.pop()
             dev = plist[0].device
-            b1, b2 = group["betas"]
             amsgrad = bool(group.get("amsgrad", False))
             decoupled = bool(group.get("decoupled_weight_decay", False))
-            if amsgrad or decoupled:
-                self._opt_step(gi, group, plist, amsgrad, decoupled, coef,
-                               dstep if self.capturable else step)
-                continue
-            _, dev_table, nchunks, n, _ = self._table(gi, plist)
-            if self.capturable and (torch.is_tensor(lr) or coef is not None):
-                if not torch.is_tensor(lr):  # (a float lr next to clipping)
-                    lr = self._lr_tensor(gi, lr, dev)
-                hip_lib.check(lib.stgcn_adam_step_dev2(
-                    hip_lib.ptr(dev_table), n, nchunks, hip_lib.ptr(lr), hip_lib.ptr(coef),
-                    b1, b2, group["eps"], group["weight_decay"], hip_lib.ptr(dstep),
-                    hip_lib.stream_handle(dev)))
-            elif self.capturable:
-                hip_lib.check(lib.stgcn_adam_step_dev(
-                    hip_lib.ptr(dev_table), n, nchunks, group["lr"], b1, b2,
-                    group["eps"], group["weight_decay"], hip_lib.ptr(dstep),
-                    hip_lib.stream_handle(dev)))
-            else:
-                hip_lib.check(lib.stgcn_adam_step(
-                    hip_lib.ptr(dev_table), n, nchunks, group["lr"], b1, b2,
-                    group["eps"], group["weight_decay"], step, hip_lib.stream_handle(dev)))
+            if coef is not None and not torch.is_tensor(lr) and not (amsgrad or decoupled):
+                # (a float lr next to clipping, on a group with neither option, is
+                # rounded to float32; DESIGN.md "Optimizers" records the asymmetry)
+                lr = self._lr_tensor(gi, lr, dev)
+            tabs = []
+            for p in plist:
+                st = self.state[p]
+                vmax = None
+                if amsgrad:
+                    if "max_exp_avg_sq" not in st:
+                        if torch.cuda.is_current_stream_capturing():
+                            raise RuntimeError("FusedAdam: capture a step only after an eager "
+                                               "step of the same parameters (GraphedStep warm-up)")
+                        st["max_exp_avg_sq"] = torch.zeros_like(
+                            p, memory_format=torch.preserve_format)
+                    vmax = st["max_exp_avg_sq"]
+                    _check_f32(vmax, "max_exp_avg_sq")
+                tabs.append(hip_lib.OptTensor(
+                    p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(),
+                    st["exp_avg_sq"].data_ptr(), None if vmax is None else vmax.data_ptr(),
+                    p.numel(), 0, 0))
+            b1, b2 = group["betas"]
+            flags = (hip_lib.OPT_AMSGRAD if amsgrad else 0) | \
+                (hip_lib.OPT_DECOUPLED_WD if decoupled else 0)
+            desc = hip_lib.OptDesc(
+                hip_lib.OPT_ADAM, flags, 0.0 if torch.is_tensor(lr) else float(lr), b1, b2,
+                group["eps"], group["weight_decay"], 0 if self.capturable else step,
+                hip_lib.ptr(lr) if torch.is_tensor(lr) else None, hip_lib.ptr(coef),
+                hip_lib.ptr(dstep) if self.capturable else None)
+            _, dev_table, nchunks, n, _ = self._table(
+                gi, hip_lib.OptTensor, tabs, lib.stgcn_opt_table_bytes,
+                lambda *a: lib.stgcn_opt_build_table(ctypes.byref(desc), *a), dev)
+            hip_lib.check(lib.stgcn_opt_step(
+                ctypes.byref(desc), hip_lib.ptr(dev_table), n, nchunks,
+                hip_lib.stream_handle(dev)))
         return loss
 
-    def _opt_step(self, gi, group, plist, amsgrad, decoupled, coef, step):
-        """The group's step through stgcn_opt_step (AMSGrad / decoupled decay);
-        step: the device count (capturable) or this step's host count."""
-        dev = plist[0].device
-        tabs = []
-        for p in plist:
-            st = self.state[p]
-            vmax = None
-            if amsgrad:
-                if "max_exp_avg_sq" not in st:
-                    if torch.cuda.is_current_stream_capturing():
-                        raise RuntimeError("FusedAdam: capture a step only after an eager step "
-                                           "of the same parameters (GraphedStep warm-up)")
-                    st["max_exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                vmax = st["max_exp_avg_sq"]
-                _check_f32(vmax, "max_exp_avg_sq")
-            tabs.append(hip_lib.OptTensor(
-                p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(),
-                st["exp_avg_sq"].data_ptr(), None if vmax is None else vmax.data_ptr(),
-                p.numel(), 0, 0))
-        lr = group["lr"]
-        b1, b2 = group["betas"]
-        flags = (hip_lib.OPT_AMSGRAD if amsgrad else 0) | \
-            (hip_lib.OPT_DECOUPLED_WD if decoupled else 0)
-        desc = hip_lib.OptDesc(
-            hip_lib.OPT_ADAM, flags, 0.0 if torch.is_tensor(lr) else float(lr), b1, b2,
-            group["eps"], group["weight_decay"], 0 if self.capturable else step,
-            hip_lib.ptr(lr) if torch.is_tensor(lr) else None, hip_lib.ptr(coef),
-            hip_lib.ptr(step) if self.capturable else None)
-        _, dev_table, nchunks, n, _ = self._opt_table(gi, desc, tabs, dev)
-        hip_lib.check(hip_lib.lib().stgcn_opt_step(
-            ctypes.byref(desc), hip_lib.ptr(dev_table), n, nchunks, hip_lib.stream_handle(dev)))
-
-    def _opt_table(self, gi, desc, tabs, dev):
-        """_table over stgcn_opt_tensor_t entries (the stgcn_opt_step route): (key,
-        device table, chunks, ntensors, host table) of the OptTensor list
-        ``tabs``; desc: the OptDesc whose state slots the entries must carry."""
-        lib = hip_lib.lib()
-        key = ("opt",) + tuple((t.param, t.grad, t.s0, t.s1, t.s2, t.numel, t.flags) for t in tabs)
+    def _table(self, gi, entry, tabs, table_bytes, build, dev):
+        """(key, device table, chunks, ntensors, host table) of the ``entry``
+        structs ``tabs`` (hip_lib.OptTensor for a step, hip_lib.AdamTensor for the
+        gradient norm), cached under ``gi`` and rebuilt when a field changed.
+        table_bytes(n) / build(array, n, host pointer, bytes, chunks out): the
+        library's pair for that entry type."""
+        names = [f for f, _ in entry._fields_]
+        key = (entry,) + tuple(tuple(getattr(t, f) for f in names) for t in tabs)
         cached = self._tables.get(gi)
         if cached is None or cached[0] != key:
             n = len(tabs)
-            nbytes = lib.stgcn_opt_table_bytes(n)
-            if torch.cuda.is_current_stream_capturing():
-                host = self._spare.pop(gi, None)
-                if host is None or host.numel() < nbytes:
-                    raise RuntimeError("FusedAdam: capture a step only after an eager "
-                                       "step of the same parameters (GraphedStep warm-up)")
-                self._captured.append(host)  # (read by every replay: never freed)
-            else:
-                host = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
-                if self.capturable:
-                    self._spare[gi] = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
-            chunks = ctypes.c_int64(0)
-            arr = (hip_lib.OptTensor * n)(*tabs)
-            hip_lib.check(lib.stgcn_opt_build_table(
-                ctypes.byref(desc), arr, n,
-                ctypes.c_void_p(host.data_ptr()), nbytes, ctypes.byref(chunks)))
-            dev_table = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            dev_table.copy_(host, non_blocking=True)
-            cached = (key, dev_table, chunks.value, n, host)
-            self._tables[gi] = cached
-        return cached
-
-    def _table(self, gi, plist):
-        """(key, device table, chunks, ntensors, host table) of the tensors of
-        ``plist``, cached under ``gi`` and rebuilt when a pointer changed."""
-        lib = hip_lib.lib()
-        tabs = [hip_lib.AdamTensor(p.data_ptr(), p.grad.data_ptr(),
-                                   self.state[p]["exp_avg"].data_ptr(),
-                                   self.state[p]["exp_avg_sq"].data_ptr(), p.numel())
-                for p in plist]
-        key = tuple((t.param, t.grad, t.exp_avg, t.exp_avg_sq, t.numel) for t in tabs)
-        dev = plist[0].device
-        cached = self._tables.get(gi)
-        if cached is None or cached[0] != key:
-            n = len(tabs)
-            nbytes = lib.stgcn_adam_table_bytes(n)
+            nbytes = table_bytes(n)
             if torch.cuda.is_current_stream_capturing():
                 # (no pinned allocation inside a capture: the spare buffer
                 # the last eager build left, never yet read by a copy)
@@ -464,9 +399,8 @@ class FusedAdam(torch.optim.Optimizer):
                 if self.capturable:
                     self._spare[gi] = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
             chunks = ctypes.c_int64(0)
-            arr = (hip_lib.AdamTensor * n)(*tabs)
-            hip_lib.check(lib.stgcn_adam_build_table(arr, n, ctypes.c_void_p(host.data_ptr()),
-                                                     nbytes, ctypes.byref(chunks)))
+            hip_lib.check(build((entry * n)(*tabs), n, ctypes.c_void_p(host.data_ptr()), nbytes,
+                                ctypes.byref(chunks)))
             dev_table = torch.empty(nbytes, dtype=torch.uint8, device=dev)
             dev_table.copy_(host, non_blocking=True)
             cached = (key, dev_table, chunks.value, n, host)
@@ -474,8 +408,8 @@ class FusedAdam(torch.optim.Optimizer):
         return cached
 
     def _lr_tensor(self, gi, lr, dev):
-        """A float lr as the device word stgcn_adam_step_dev2 reads (the clipped
-        step with a float lr; the value rounded to float32, as a tensor lr is):
+        """A float lr as a device word (the clipped step of a group with neither
+        amsgrad nor decoupled decay; the value rounded to float32, as a tensor lr is):
         rewritten when the value changes; inside a capture the write is part of
         the graph, so a captured step keeps its capture's value, like the
         by-value call."""
@@ -500,7 +434,13 @@ class FusedAdam(torch.optim.Optimizer):
             if gp:
                 self._device_step(gp)
         dev = plist[0].device
-        _, dev_table, nchunks, n, _ = self._table("norm", plist)
+        tabs = [hip_lib.AdamTensor(p.data_ptr(), p.grad.data_ptr(),
+                                   self.state[p]["exp_avg"].data_ptr(),
+                                   self.state[p]["exp_avg_sq"].data_ptr(), p.numel())
+                for p in plist]
+        _, dev_table, nchunks, n, _ = self._table(
+            "norm", hip_lib.AdamTensor, tabs, lib.stgcn_adam_table_bytes,
+            lib.stgcn_adam_build_table, dev)
         if self.grad_norm is None:
             self.grad_norm = torch.zeros((), device=dev, dtype=torch.float32)
             self.clip_coef = torch.ones((), device=dev, dtype=torch.float32)

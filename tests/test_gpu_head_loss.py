@@ -98,8 +98,7 @@ def test_parity_grid(pkg, shape, eps, weighted):
 
 
 def _raw(pkg, c, lab, flags, eps, w=None, metrics=None, topk=1, from_u=False):
-    """stgcn_head_eval_loss / _u itself (head_eval routes default options to
-    stgcn_head_eval): (loss, logits, pred, lossv, denom)."""
+    """stgcn_head_eval_loss / _u itself: (loss, logits, pred, lossv, denom)."""
     hl = pkg.hip_lib
     y, W, b = _dev(c, "y", "W", "b")
     N, C = y.shape[0], y.shape[1]
@@ -119,6 +118,29 @@ def _raw(pkg, c, lab, flags, eps, w=None, metrics=None, topk=1, from_u=False):
         hl.check(hl.lib().stgcn_head_eval_loss(ctypes.byref(d), *[hl.ptr(t) for t in (
             y, *tail)], hl.stream_handle(y.device)))
     return loss, logits, pred, lossv, denom
+
+
+def _raw_eval(pkg, c, lab, metrics=None, topk=1, from_u=False):
+    """stgcn_head_eval / _u itself (nothing in Python calls them: head_eval goes
+    through stgcn_head_eval_loss): (loss, logits, pred, lossv)."""
+    hl = pkg.hip_lib
+    y, W, b = _dev(c, "y", "W", "b")
+    N, C = y.shape[0], y.shape[1]
+    classes = W.shape[0]
+    d = hl.EvalDesc(N, C, y[0, 0].numel(), classes, topk)
+    pooled = torch.empty(N, C, device=DEV)
+    logits = torch.empty(N, classes, device=DEV)
+    lossv, loss = torch.empty(N, device=DEV), torch.empty((), device=DEV)
+    pred = torch.empty(N, device=DEV, dtype=torch.int32)
+    tail = (W, b, lab, pooled, logits, lossv, loss, pred,
+            None if metrics is None else metrics.buf)
+    if from_u:
+        hl.check(hl.lib().stgcn_head_eval_u(ctypes.byref(d), *[hl.ptr(t) for t in (
+            *_dev(c, "U", "stats2", "g2", "b2"), *tail)], hl.stream_handle(y.device)))
+    else:
+        hl.check(hl.lib().stgcn_head_eval(ctypes.byref(d), *[hl.ptr(t) for t in (
+            y, *tail)], hl.stream_handle(y.device)))
+    return loss, logits, pred, lossv
 
 
 def test_one_clip(pkg):
@@ -154,17 +176,18 @@ def test_default_options_have_the_eval_heads_bits(pkg, shape, ignored, from_u):
     m0, m1 = to.EvalMetrics(classes, 3, device=DEV), to.EvalMetrics(classes, 3, device=DEV)
     fu = tuple(_dev(c, "U", "stats2", "g2", "b2")) if from_u else None
     y = None if from_u else y
-    loss0, logits0, pred0, lossv0 = to.head_eval(y, W, b, lab, metrics=m0, from_u=fu)
+    loss0, logits0, pred0, lossv0 = _raw_eval(pkg, c, lab, metrics=m0, topk=3, from_u=from_u)
     loss, logits, pred, lossv, denom = _raw(pkg, c, lab, 0, 0.0, metrics=m1, topk=3,
                                             from_u=from_u)
     assert torch.equal(loss, loss0) and torch.equal(logits, logits0)
     assert torch.equal(lossv, lossv0) and torch.equal(pred, pred0)
     assert torch.equal(m0.buf, m1.buf)
     assert denom.item() == int(((lab >= 0) & (lab < classes)).sum())
-    # the Python route with its defaults spelled out is today's call
-    loss2, logits2, _, _ = to.head_eval(y, W, b, lab, from_u=fu, weight=None,
-                                        label_smoothing=0.0)
-    assert torch.equal(loss2, loss0) and torch.equal(logits2, logits0)
+    # the Python route, with its defaults left out and spelled out
+    for kw in ({}, dict(weight=None, label_smoothing=0.0)):
+        loss2, logits2, pred2, lossv2 = to.head_eval(y, W, b, lab, from_u=fu, **kw)
+        assert torch.equal(loss2, loss0) and torch.equal(logits2, logits0)
+        assert torch.equal(lossv2, lossv0) and torch.equal(pred2, pred0)
 
 
 @pytest.mark.parametrize("eps", [0.0, 0.1])

@@ -11,6 +11,8 @@ Gates. Against torch on the CPU: FusedAdam's own gate
 (tests/test_gpu_train_ops.py), |d| <= 2e-6 |ref| + 1e-7 per element and states
 < 1e-6 rel-to-max. Everything that compares two runs of this library compares
 bits."""
+import ctypes
+
 import numpy as np
 import pytest
 import torch
@@ -75,38 +77,79 @@ def test_adamw_and_amsgrad_match_torch(pkg, decoupled, wd, amsgrad, capturable):
         assert "max_exp_avg_sq" not in opt.state[dut[0]]
 
 
+def _legacy_adam(pkg, form, max_norm):
+    """Five steps through the Adam-format entry points by raw ctypes calls:
+    stgcn_adam_build_table over the eight tensors (fresh gradients, so a new
+    table every step), then stgcn_adam_step ("host_step"), stgcn_adam_step_dev
+    ("device_step") or stgcn_adam_step_dev2 with a device lr and the grad_coef of
+    a raw stgcn_grad_norm call. Returns (params, exp_avg, exp_avg_sq, clip_coef)."""
+    hl = pkg.hip_lib
+    lib = hl.lib()
+    dev = torch.device(DEV)
+    ps = [p.clone().to(DEV) for p in P0]
+    ms, vs = [torch.zeros_like(p) for p in ps], [torch.zeros_like(p) for p in ps]
+    n = len(ps)
+    step_dev = torch.zeros((), device=DEV)
+    lr_dev = torch.zeros((), device=DEV)
+    norm, coef = torch.zeros((), device=DEV), torch.ones((), device=DEV)
+    nbytes = lib.stgcn_adam_table_bytes(n)
+    for k, (v, gs) in enumerate(zip(LRS, GRADS)):
+        grads = [g.to(DEV) for g in gs]
+        arr = (hl.AdamTensor * n)(*[
+            hl.AdamTensor(p.data_ptr(), g.data_ptr(), m.data_ptr(), q.data_ptr(), p.numel())
+            for p, g, m, q in zip(ps, grads, ms, vs)])
+        host = torch.empty(nbytes, dtype=torch.uint8)
+        chunks = ctypes.c_int64(0)
+        hl.check(lib.stgcn_adam_build_table(arr, n, ctypes.c_void_p(host.data_ptr()), nbytes,
+                                            ctypes.byref(chunks)))
+        table = host.to(DEV)
+        args = (hl.ptr(table), n, chunks.value)
+        if form == "host_step":
+            hl.check(lib.stgcn_adam_step(*args, 1e-2, 0.9, 0.999, 1e-8, 0.0, k + 1,
+                                         hl.stream_handle(dev)))
+        elif form == "device_step":
+            hl.check(lib.stgcn_adam_step_dev(*args, 1e-2, 0.9, 0.999, 1e-8, 0.0,
+                                             hl.ptr(step_dev), hl.stream_handle(dev)))
+        else:
+            lr_dev.fill_(v)
+            partials = torch.empty(lib.stgcn_grad_norm_bytes(chunks.value) // 8, device=DEV,
+                                   dtype=torch.float64)
+            hl.check(lib.stgcn_grad_norm(*args, max_norm, hl.ptr(partials), hl.ptr(norm),
+                                         hl.ptr(coef), hl.stream_handle(dev)))
+            hl.check(lib.stgcn_adam_step_dev2(*args, hl.ptr(lr_dev), hl.ptr(coef), 0.9, 0.999,
+                                              1e-8, 0.0, hl.ptr(step_dev),
+                                              hl.stream_handle(dev)))
+        torch.cuda.synchronize()  # (the table and the gradients live until the step has run)
+    return ps, ms, vs, coef
+
+
 @pytest.mark.parametrize("form", ["host_step", "device_step", "device_lr_and_clip"])
 def test_new_route_without_its_options_is_todays_fused_adam(pkg, form):
-    """FusedAdamW(weight_decay=0) runs stgcn_opt_step's kernel with neither
-    option in effect; FusedAdam() runs stgcn_adam_step / _dev / _dev2. The same
-    bits in all three launch forms."""
+    """FusedAdam() runs stgcn_opt_step's kernel with neither option in effect;
+    stgcn_adam_step / _dev / _dev2, which nothing in Python launches, are called
+    here directly (_legacy_adam). The same bits in all three launch forms."""
+    max_norm = 0.5 * min(_norm(gs) for gs in GRADS)
     kw = {"host_step": dict(lr=1e-2),
           "device_step": dict(lr=1e-2, capturable=True),
-          "device_lr_and_clip": dict(capturable=True,
-                                     max_grad_norm=0.5 * min(_norm(gs) for gs in GRADS))}[form]
-    pa, pb = _dev_params(), _dev_params()
-    if form == "device_lr_and_clip":
-        oa = pkg.FusedAdam(pa, lr=torch.tensor(1e-2, device=DEV), **kw)
-        ob = pkg.FusedAdamW(pb, lr=torch.tensor(1e-2, device=DEV), weight_decay=0, **kw)
-    else:
-        oa = pkg.FusedAdam(pa, **kw)
-        ob = pkg.FusedAdamW(pb, weight_decay=0, **kw)
-    assert ob.param_groups[0]["decoupled_weight_decay"] and not ob.param_groups[0]["amsgrad"]
+          "device_lr_and_clip": dict(lr=torch.tensor(1e-2, device=DEV), capturable=True,
+                                     max_grad_norm=max_norm)}[form]
+    pa, ma, va, coef_a = _legacy_adam(pkg, form, max_norm)
+    pb = _dev_params()
+    ob = pkg.FusedAdam(pb, **kw)
+    assert not ob.param_groups[0]["decoupled_weight_decay"] and not ob.param_groups[0]["amsgrad"]
     for v, gs in zip(LRS, GRADS):
         if form == "device_lr_and_clip":
-            oa.param_groups[0]["lr"].fill_(v)
             ob.param_groups[0]["lr"].fill_(v)
-        for p, q, g in zip(pa, pb, gs):
-            p.grad, q.grad = g.to(DEV), g.to(DEV)
-        oa.step()
+        for q, g in zip(pb, gs):
+            q.grad = g.to(DEV)
         ob.step()
     torch.cuda.synchronize()
     if form == "device_lr_and_clip":
-        assert torch.equal(oa.clip_coef, ob.clip_coef) and float(ob.clip_coef) < 1.0
-    for a, b in zip(pa, pb):
-        assert torch.equal(a.detach(), b.detach())
-        for k in AMS_KEYS[:2]:
-            assert torch.equal(oa.state[a][k], ob.state[b][k]), k
+        assert torch.equal(coef_a, ob.clip_coef) and float(ob.clip_coef) < 1.0
+    for a, m, v, b in zip(pa, ma, va, pb):
+        assert torch.equal(a, b.detach())
+        assert torch.equal(m, ob.state[b]["exp_avg"])
+        assert torch.equal(v, ob.state[b]["exp_avg_sq"])
 
 
 @pytest.mark.parametrize("decoupled", [False, True])

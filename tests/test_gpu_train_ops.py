@@ -7,6 +7,8 @@ a different order); Adam parameters within 2e-6 relative per element over 5
 steps, moments within 1e-6 rel-to-max (the update is elementwise in torch's
 op order; CPU and GPU may differ in fma contraction by an ulp, and moments
 that cross 0 make per-element relative error meaningless)."""
+import ctypes
+
 import numpy as np
 import pytest
 import torch
@@ -40,6 +42,46 @@ def test_head_matches_torch(pkg, N, C, T, V, classes):
     assert rel_to_max(logits.cpu().numpy(), logits64.detach().numpy()) < 1e-5
     for got, want in ((yd.grad, y64.grad), (Wd.grad, W64.grad), (bd.grad, b64.grad)):
         assert rel_to_max(got.cpu().numpy(), want.numpy()) < 1e-5
+
+
+@pytest.mark.parametrize("from_u", [False, True])
+def test_training_head_bad_label_rule(pkg, from_u):
+    """stgcn_head_fwd / _fwd_u, called directly: a label outside [0, classes)
+    gives NaN in its lossv and in loss, where head_eval (the same row kernel's
+    other instantiation) ignores the clip: 0 and a finite loss. The logits and
+    the valid clip's loss are head_eval's bits."""
+    hl = pkg.hip_lib
+    N, C, T, V, classes = 3, 64, 4, 50, 7
+    g = torch.Generator().manual_seed(11)
+    U = torch.randn(N, C, T, V, generator=g)
+    stats2 = torch.cat([torch.randn(C, generator=g), torch.rand(C, generator=g) + 0.5])
+    g2, b2 = torch.randn(C, generator=g), torch.randn(C, generator=g)
+    sh = (1, C, 1, 1)
+    y = torch.clamp_min((U - stats2[:C].view(sh)) * (stats2[C:] * g2).view(sh) + b2.view(sh), 0.0)
+    W = torch.randn(classes, C, generator=g) * 0.3
+    b = torch.randn(classes, generator=g) * 0.3
+    U, stats2, g2, b2, y, W, b = (t.contiguous().to(DEV) for t in (U, stats2, g2, b2, y, W, b))
+    lab = torch.tensor([2, -1, 7], device=DEV)
+    d = hl.HeadDesc(N, C, T * V, classes)
+    pooled = torch.empty(N, C, device=DEV)
+    logits = torch.empty(N, classes, device=DEV)
+    lossv, loss = torch.empty(N, device=DEV), torch.empty((), device=DEV)
+    tail = (W, b, lab, pooled, logits, lossv, loss)
+    if from_u:
+        hl.check(hl.lib().stgcn_head_fwd_u(ctypes.byref(d), *[hl.ptr(t) for t in (
+            U, stats2, g2, b2, *tail)], hl.stream_handle(y.device)))
+        ev = pkg.train_ops.head_eval(None, W, b, lab, from_u=(U, stats2, g2, b2))
+    else:
+        hl.check(hl.lib().stgcn_head_fwd(ctypes.byref(d), *[hl.ptr(t) for t in (y, *tail)],
+                                         hl.stream_handle(y.device)))
+        ev = pkg.train_ops.head_eval(y, W, b, lab)
+    loss_e, logits_e, _, lossv_e = ev
+    torch.cuda.synchronize()
+    assert torch.equal(logits, logits_e)
+    assert torch.equal(lossv[0], lossv_e[0]) and torch.isfinite(lossv[0]) and lossv[0] > 0
+    assert torch.isnan(lossv[1]) and torch.isnan(lossv[2]) and torch.isnan(loss)
+    assert lossv_e[1] == 0 and lossv_e[2] == 0 and torch.isfinite(loss_e)
+    assert torch.equal(loss_e, lossv_e[0])  # (the mean over the one valid clip)
 
 
 def test_head_in_stack_matches_torch_head(pkg):
