@@ -57,7 +57,8 @@
  *         grad_coef, norm_out, coef_out 4; stgcn_grad_norm's partials 8.
  *       STGCN_FEATURE_INPUT_STAGE (stgcn_input_stage): x 16 bytes, like a block
  *         tensor; src its element's own 4 (fp32) or 8 (fp64) bytes; the clip
- *         table 8; status 4.
+ *         table 8; status 4. STGCN_FEATURE_INPUT_MOVE (stgcn_input_stage_move): the
+ *         same, and the move table 8.
  *       STGCN_FEATURE_OPTIMIZERS (stgcn_opt_*): the device table 8; every param /
  *         grad / s0 / s1 / s2 of a table entry, lr_dev, grad_coef and step_dev 4.
  *     A caller with a misaligned read-only input for a 16-byte argument passes an
@@ -304,6 +305,9 @@ const char *stgcn_last_error(void);
 #define STGCN_FEATURE_HEAD_LOSS 32 /* stgcn_loss_check, stgcn_head_eval_loss / _u: class
                                     * weights and label smoothing in the evaluation head
                                     * (the training head takes neither yet)             */
+#define STGCN_FEATURE_INPUT_MOVE 64 /* stgcn_input_move_check / stgcn_input_stage_move:
+                                    * per-frame interpolated rotation, scale and translation
+                                    * ("random moving") in the input stage              */
 int stgcn_features(void);
 
 /* Validate a descriptor without touching the GPU (0 = supported). */
@@ -682,8 +686,10 @@ int stgcn_opt_step(const stgcn_opt_desc_t *d, const void *dev_table, int ntensor
  *   frame = clips[n].first_frame + (t mod clips[n].frames)
  * (np.pad "wrap"; a clip of T_out frames or more gives its first T_out),
  *   x[n, j, t, v] = src[frame, v, 0] * m[0][j] + src[frame, v, 1] * m[1][j]
- * for j = 0, 1 when flags bit 0 is set: two products and a sum in fp64 whatever
- * the source type (no fused multiply-add), rounded once to fp32; m is the upper
+ * for j = 0, 1 when flags bit 0 is set: in fp64 whatever the source type, as one
+ * product and one fused multiply-add, fma(src[.., 0], m[0][j], src[.., 1] *
+ * m[1][j]) (what the kernel has always computed; within 2^-52 relative of each
+ * term of the unfused form), rounded once to fp32; m is the upper
  * left 2x2 of the reference's 3x3 matrix (its third homogeneous coordinate is
  * 0: translations do not move points). Without the bit channels 0 and 1 are
  * cast like channels 2 .. C - 1: bit-exact, non-finite values included.
@@ -710,6 +716,52 @@ typedef struct stgcn_clip { /* 48 bytes, device memory, N of them               
 int stgcn_input_check(const stgcn_input_desc_t *d);
 int stgcn_input_stage(const stgcn_input_desc_t *d, const void *src, const stgcn_clip_t *clips,
                       float *x, int32_t *status, void *stream);
+
+/* ---------------------------------------------------------------------------
+ * STGCN_FEATURE_INPUT_MOVE: stgcn_input_stage with ST-GCN's "random moving"
+ * (the training augmentation of the ST-GCN recipe, feeder/tools.py random_move;
+ * the TODO of src/data/augmentation.py:48): rotation angle, scale and
+ * translation given at up to 4 key frames, interpolated linearly over the
+ * output frames and applied per frame, after the clip's own 2x2 matrix.
+ * Unlike that matrix (src/data/augmentation.py:56-59 multiplies [x, y, 0], so
+ * the reference drops its translations, and stgcn_clip_t keeps doing so), the
+ * translation here moves the points.
+ *
+ * moves is a DEVICE table of N records, read when the kernel runs, like clips.
+ * For output frame t of clip n in segment k (frame[k] <= t < frame[k + 1]; a
+ * last frame t == frame[nk - 1] belongs to the last segment) each of angle,
+ * scale, tx, ty is
+ *   p(t) = p[k] + (double)(t - frame[k]) *
+ *                 ((p[k + 1] - p[k]) / (double)(frame[k + 1] - frame[k]))
+ * and with c = cos(a) * s, sn = sin(a) * s and (x, y) the point after the
+ * clip's matrix (kept in fp64; the plain source values without the flag)
+ *   x[n, 0, t, v] = (c * x - sn * y) + tx
+ *   x[n, 1, t, v] = (sn * x + c * y) + ty
+ * all in fp64, every operation rounded on its own (no fused multiply-add), one
+ * rounding to fp32 at the end. Channels 2 .. C - 1 are cast as before.
+ * nk == 0: no move, the clip takes stgcn_input_stage's path and has its bits.
+ * A record is invalid when nk is not 0, 2, 3 or 4, frame[0] != 0, the first nk
+ * frames do not strictly increase, frame[nk - 1] < T_out - 1, or one of the
+ * first nk values of angle, scale, tx, ty is not finite: the clip is written as
+ * zeros without reading src, and status[n] has bit 1 set. status[n] =
+ * (invalid clip entry ? 1 : 0) | (invalid move record ? 2 : 0), written for
+ * every clip at every launch with plain stores.
+ * moves == NULL: the call is stgcn_input_stage. Alignment: moves 8 bytes, the
+ * rest as stgcn_input_stage. */
+typedef struct stgcn_move { /* 160 bytes, device memory, N of them              */
+  int32_t nk;               /* key frames: 0 (no move) or 2..4                  */
+  int32_t frame[4];         /* frame[0] = 0 < ... < frame[nk - 1] >= T_out - 1  */
+  int32_t reserved0;
+  double angle[4];          /* radians                                          */
+  double scale[4];
+  double tx[4], ty[4];
+  int64_t reserved1;
+} stgcn_move_t;
+/* stgcn_input_check for the move launch (the same limits). */
+int stgcn_input_move_check(const stgcn_input_desc_t *d);
+int stgcn_input_stage_move(const stgcn_input_desc_t *d, const void *src,
+                           const stgcn_clip_t *clips, const stgcn_move_t *moves, float *x,
+                           int32_t *status, void *stream);
 
 #ifdef __cplusplus
 }

@@ -3,7 +3,7 @@
 // x (N, C, T_out, V) fp32 in ONE memory-bound kernel: the loop padding of
 // src/data/util.py:12-30 (np.pad "wrap" == frame t mod T_i), the per-clip 2x2
 // part of the augmentation matrix (src/data/augmentation.py:8-69, evaluated in
-// fp64 like numpy, rounded once to fp32), the fp32 cast and the NTVC -> NCTV
+// fp64, rounded once to fp32), the fp32 cast and the NTVC -> NCTV
 // transpose of lightning_model.py:101.
 //
 // One thread per output point (n, t, v): it loads the point's C_src source
@@ -15,6 +15,10 @@
 // kernel RUNS, so a captured launch sees the table of each replay; an entry
 // that does not lie inside [0, src_frames) zero-fills its clip, flags it in
 // status[] and reads nothing of src.
+//
+// STGCN_FEATURE_INPUT_MOVE (k_input_stage_move, below): the same launch with one
+// stgcn_move_t per clip -- rotation, scale and translation interpolated over the
+// frames and applied per frame ("random moving"), validated in the kernel too.
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -65,8 +69,10 @@ k_input_stage(const S *__restrict__ src, const stgcn_clip_t *__restrict__ clips,
   const Point<S, CS> pt =
       *reinterpret_cast<const Point<S, CS> *>(src + (frame * V + v) * (int64_t)CS);
   if (clip.flags & 1) {
-    // out_j = x m[0][j] + y m[1][j]: two products and one sum, each rounded to
-    // fp64 (no fused multiply-add: numpy's arithmetic), then one rounding to fp32
+    // out_j = x m[0][j] + y m[1][j] in fp64, then one rounding to fp32. As compiled
+    // this is one product and one fused multiply-add, fma(x, m[0][j], y m[1][j]):
+    // __dmul_rn / __dadd_rn are plain operators under the default contraction
+    // (see store_point below, which writes that form out and must keep matching)
     const double px = (double)pt.c[0], py = (double)pt.c[1];
     out[0] = (float)__dadd_rn(__dmul_rn(px, clip.m[0]), __dmul_rn(py, clip.m[2]));
     out[plane] = (float)__dadd_rn(__dmul_rn(px, clip.m[1]), __dmul_rn(py, clip.m[3]));
@@ -79,15 +85,171 @@ k_input_stage(const S *__restrict__ src, const stgcn_clip_t *__restrict__ clips,
     if (c < C) out[(int64_t)c * plane] = (float)pt.c[c];
 }
 
+// ---- STGCN_FEATURE_INPUT_MOVE ------------------------------------------------
+
+// From here on every fp64 operation is rounded on its own: the move's arithmetic
+// is numpy's, operation by operation (data.apply_moves_reference). Plain
+// operators, not __dmul_rn / __dadd_rn: those are header functions compiled in the
+// default mode, whose product and sum the compiler would fuse again.
+#pragma clang fp contract(off)
+
+// k_input_stage's work on one point of a valid clip, for a clip without a move,
+// with its bits. HIP's __dmul_rn / __dadd_rn are header functions over plain
+// operators, and under the compiler's default contraction k_input_stage's
+// transform is one product and one fused multiply-add in all six instances,
+// out_j = fma(x, m[0][j], y m[1][j]) (v_mul_f64 + v_fmac_f64 in its code objects),
+// not two products and a sum. That is what it has always computed and it is
+// kept; it is written out here, so that this kernel does not depend on the
+// compiler fusing the same pair again. The nk = 0 bit-equality does depend on
+// the compiler still fusing that pair in k_input_stage itself, whose text is left
+// alone so that its code objects stay the parent's; tests/test_gpu_input_move.py
+// (test_no_move_has_the_plain_stage_bits) fails if a compiler ever stops.
+template <typename S, int CS>
+__device__ __forceinline__ void store_point(const Point<S, CS> &pt, const stgcn_clip_t &clip,
+                                            float *out, int plane, int C) {
+  if (clip.flags & 1) {
+    const double px = (double)pt.c[0], py = (double)pt.c[1];
+    out[0] = (float)__builtin_fma(px, clip.m[0], py * clip.m[2]);
+    out[plane] = (float)__builtin_fma(px, clip.m[1], py * clip.m[3]);
+  } else {
+    out[0] = (float)pt.c[0];
+    out[plane] = (float)pt.c[1];
+  }
+#pragma unroll
+  for (int c = 2; c < CS; ++c)
+    if (c < C) out[(int64_t)c * plane] = (float)pt.c[c];
+}
+
+// nk = 0, or 2..4 key frames from 0, strictly increasing, the last at T_out - 1
+// or later, and finite parameters (uniform per workgroup)
+__device__ __forceinline__ bool move_ok(const stgcn_move_t &mv, int T_out) {
+  if (mv.nk == 0) return true;
+  if (mv.nk < 2 || mv.nk > 4 || mv.frame[0] != 0) return false;
+  bool ok = true;
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    if (i < mv.nk) {
+      if (i > 0) ok = ok && mv.frame[i] > mv.frame[i - 1];
+      ok = ok && isfinite(mv.angle[i]) && isfinite(mv.scale[i]) && isfinite(mv.tx[i]) &&
+           isfinite(mv.ty[i]);
+    }
+  // (constant indices only: an indexed access would put the record in scratch)
+  const int last = mv.nk == 2 ? mv.frame[1] : mv.nk == 3 ? mv.frame[2] : mv.frame[3];
+  return ok && last >= T_out - 1;
+}
+
+// p(t) = p_k + (t - f_k) * ((p_k1 - p_k) / (f_k1 - f_k)): np.linspace's start +
+// i * step, every operation rounded on its own
+__device__ __forceinline__ double lerp_key(double pk, double pk1, double i, double span) {
+  return pk + i * ((pk1 - pk) / span);
+}
+
+struct Affine {
+  double c, sn, tx, ty;
+};
+
+// frame t of a valid record with nk >= 2: its segment by selects (the record
+// sits in scalar registers: no indexed access), the four parameters, then
+// c = cos(a) * s, sn = sin(a) * s
+__device__ __forceinline__ Affine frame_affine(const stgcn_move_t &mv, int t) {
+  const bool s1 = mv.nk > 2 && t >= mv.frame[1], s2 = mv.nk > 3 && t >= mv.frame[2];
+#define MOVE_SEL(a) (s2 ? a[2] : s1 ? a[1] : a[0])
+#define MOVE_SEL1(a) (s2 ? a[3] : s1 ? a[2] : a[1])
+  const int f0 = MOVE_SEL(mv.frame), f1 = MOVE_SEL1(mv.frame);
+  const double i = (double)(t - f0), span = (double)(f1 - f0);
+  const double a = lerp_key(MOVE_SEL(mv.angle), MOVE_SEL1(mv.angle), i, span);
+  const double s = lerp_key(MOVE_SEL(mv.scale), MOVE_SEL1(mv.scale), i, span);
+  Affine r;
+  r.tx = lerp_key(MOVE_SEL(mv.tx), MOVE_SEL1(mv.tx), i, span);
+  r.ty = lerp_key(MOVE_SEL(mv.ty), MOVE_SEL1(mv.ty), i, span);
+#undef MOVE_SEL
+#undef MOVE_SEL1
+  r.c = cos(a) * s;
+  r.sn = sin(a) * s;
+  return r;
+}
+
+// k_input_stage with one stgcn_move_t per clip: same grid, same point per
+// thread, same stores. A workgroup's 256 points lie in at most 255 / V + 2
+// frames; their (c, sn, tx, ty) are evaluated once, by the first threads, into
+// LDS (kMoveFrames covers V = 1), and every thread reads its frame's four
+// doubles from there.
+constexpr int kMoveFrames = kStageThreads + 1;
+
+template <typename S, int CS>
+__global__ void __launch_bounds__(kStageThreads)
+k_input_stage_move(const S *__restrict__ src, const stgcn_clip_t *__restrict__ clips,
+                   const stgcn_move_t *__restrict__ moves, float *__restrict__ x,
+                   int32_t *__restrict__ status, int C, int T_out, int V, int bpc,
+                   int64_t src_frames) {
+  __shared__ Affine frames[kMoveFrames];
+  const int n = (int)(blockIdx.x / (unsigned)bpc);
+  const int chunk = (int)(blockIdx.x - (unsigned)n * (unsigned)bpc);
+  const int plane = T_out * V;  // < 2^31 (stgcn_input_check)
+  const int64_t p64 = (int64_t)chunk * kStageThreads + (int64_t)threadIdx.x;
+  const stgcn_clip_t clip = clips[n];
+  const stgcn_move_t &mv = moves[n];  // (fields are loaded where used: uniform loads)
+  const bool clip_ok = clip.frames >= 1 && clip.first_frame >= 0 &&
+                       clip.first_frame <= src_frames - (int64_t)clip.frames;
+  const bool mv_ok = move_ok(mv, T_out);
+  if (chunk == 0 && threadIdx.x == 0) status[n] = (clip_ok ? 0 : 1) | (mv_ok ? 0 : 2);
+  const bool live = p64 < plane;
+  const int p = live ? (int)p64 : 0;
+  float *out = x + (int64_t)n * C * plane + p;
+  if (!clip_ok || !mv_ok) {  // (uniform)
+    if (live)
+      for (int c = 0; c < C; ++c) out[(int64_t)c * plane] = 0.f;
+    return;
+  }
+  // the point's source values first: the load is in flight while the frames'
+  // parameters are evaluated
+  const int t = p / V, v = p - t * V;
+  Point<S, CS> pt = {};
+  if (live) {
+    const int64_t frame = clip.first_frame + (int64_t)((unsigned)t % (unsigned)clip.frames);
+    pt = *reinterpret_cast<const Point<S, CS> *>(src + (frame * V + v) * (int64_t)CS);
+  }
+  if (mv.nk == 0) {  // (uniform) no move: k_input_stage's bits
+    if (live) store_point<S, CS>(pt, clip, out, plane, C);
+    return;
+  }
+  // the workgroup's first point is in range (bpc = ceil(plane / 256)); frames
+  // t0 .. t0 + (255 / V + 1), cut at the plane's end. Every thread of the
+  // workgroup reaches the barrier: the returns above are uniform.
+  const int t0 = (int)(((int64_t)chunk * kStageThreads) / V);
+  const int tf = t0 + (int)threadIdx.x;
+  if ((int)threadIdx.x <= (kStageThreads - 1) / V + 1 && tf < T_out)
+    frames[threadIdx.x] = frame_affine(mv, tf);
+  __syncthreads();
+  if (!live) return;
+  const Affine f = frames[t - t0];
+  double px = (double)pt.c[0], py = (double)pt.c[1];
+  if (clip.flags & 1) {  // the clip's matrix first (two products, one sum), kept in fp64
+    const double qx = px * clip.m[0] + py * clip.m[2];
+    py = px * clip.m[1] + py * clip.m[3];
+    px = qx;
+  }
+  // x' = (c x - sn y) + tx, y' = (sn x + c y) + ty, one rounding to fp32
+  out[0] = (float)((f.c * px - f.sn * py) + f.tx);
+  out[plane] = (float)((f.sn * px + f.c * py) + f.ty);
+#pragma unroll
+  for (int c = 2; c < CS; ++c)
+    if (c < C) out[(int64_t)c * plane] = (float)pt.c[c];
+}
+
 template <typename S>
 void launch_stage(const stgcn_input_desc_t *d, const void *src, const stgcn_clip_t *clips,
-                  float *x, int32_t *status, int bpc, hipStream_t s) {
+                  const stgcn_move_t *moves, float *x, int32_t *status, int bpc, hipStream_t s) {
   const dim3 grid((unsigned)((int64_t)d->N * bpc)), block(kStageThreads);
   const S *sp = (const S *)src;
-#define STAGE_CASE(CS)                                                                        \
-  case CS:                                                                                    \
-    hipLaunchKernelGGL((k_input_stage<S, CS>), grid, block, 0, s, sp, clips, x, status, d->C, \
-                       d->T_out, d->V, bpc, d->src_frames);                                   \
+#define STAGE_CASE(CS)                                                                          \
+  case CS:                                                                                      \
+    if (moves)                                                                                  \
+      hipLaunchKernelGGL((k_input_stage_move<S, CS>), grid, block, 0, s, sp, clips, moves, x,   \
+                         status, d->C, d->T_out, d->V, bpc, d->src_frames);                     \
+    else                                                                                        \
+      hipLaunchKernelGGL((k_input_stage<S, CS>), grid, block, 0, s, sp, clips, x, status, d->C, \
+                         d->T_out, d->V, bpc, d->src_frames);                                   \
     break;
   switch (d->C_src) {
     STAGE_CASE(2)
@@ -105,6 +267,7 @@ int blocks_per_clip(const stgcn_input_desc_t *d) {
 
 static_assert(sizeof(stgcn_input_desc_t) == 32, "stgcn_input_desc_t is 32 bytes");
 static_assert(sizeof(stgcn_clip_t) == 48, "stgcn_clip_t is 48 bytes");
+static_assert(sizeof(stgcn_move_t) == 160, "stgcn_move_t is 160 bytes");
 
 extern "C" {
 
@@ -126,8 +289,16 @@ int stgcn_input_check(const stgcn_input_desc_t *d) {
   return STGCN_OK;
 }
 
+int stgcn_input_move_check(const stgcn_input_desc_t *d) { return stgcn_input_check(d); }
+
 int stgcn_input_stage(const stgcn_input_desc_t *d, const void *src, const stgcn_clip_t *clips,
                       float *x, int32_t *status, void *stream) {
+  return stgcn_input_stage_move(d, src, clips, nullptr, x, status, stream);
+}
+
+int stgcn_input_stage_move(const stgcn_input_desc_t *d, const void *src,
+                           const stgcn_clip_t *clips, const stgcn_move_t *moves, float *x,
+                           int32_t *status, void *stream) {
   if (int rc = stgcn_input_check(d)) return rc;
   if (!src || !clips || !x || !status)
     return fail(STGCN_E_INVALID, "input: null argument (src, clips, x, status)");
@@ -135,11 +306,12 @@ int stgcn_input_stage(const stgcn_input_desc_t *d, const void *src, const stgcn_
   if (int rc = check_aligned({NP(src)}, d->src_f64 ? 8 : 4)) return rc;
   if (int rc = check_aligned({NP(clips)}, 8)) return rc;
   if (int rc = check_aligned({NP(status)}, 4)) return rc;
+  if (int rc = check_aligned({NP(moves)}, 8)) return rc;  // (null passes)
   const int bpc = blocks_per_clip(d);
   if (d->src_f64)
-    launch_stage<double>(d, src, clips, x, status, bpc, (hipStream_t)stream);
+    launch_stage<double>(d, src, clips, moves, x, status, bpc, (hipStream_t)stream);
   else
-    launch_stage<float>(d, src, clips, x, status, bpc, (hipStream_t)stream);
+    launch_stage<float>(d, src, clips, moves, x, status, bpc, (hipStream_t)stream);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess)
     return fail(STGCN_E_HIP, std::string("input_stage launch: ") + hipGetErrorString(e));

@@ -27,6 +27,10 @@ Beside it, the same pipeline with the per-element work on the GPU
 memory, one HIP kernel (csrc/input_stage.hip) loop-pads, applies a transform
 drawn PER CLIP as the reference's dataset does (datasets.py:154), casts and
 transposes to NCTV, into a tensor the caller may own (a GraphedStep's input).
+On top of it ST-GCN's training augmentation, which the reference leaves as a
+TODO (augmentation.py:48): ``clip_moves`` / ``apply_moves_reference`` ("random
+moving": per-frame interpolated rotation, scale and translation, applied by
+the same kernel) and ``pack_clips(crop="random")`` ("random choose").
 """
 import ctypes
 import os
@@ -212,6 +216,99 @@ def clip_transforms(n, augment=True, rng=np.random, coin=random):
     return out
 
 
+# stgcn_move_t (include/stgcn_hip.h), 160 bytes: the "random moving" of ST-GCN's
+# training recipe (feeder/tools.py random_move), one record per clip
+MOVE_DTYPE = np.dtype({"names": ["nk", "frame", "angle", "scale", "tx", "ty"],
+                       "formats": ["<i4", ("<i4", (4,))] + [("<f8", (4,))] * 4,
+                       "offsets": [0, 4, 24, 56, 88, 120], "itemsize": 160})
+assert MOVE_DTYPE.itemsize == ctypes.sizeof(hip_lib.Move) == 160
+MOVE_ANGLES = (-10.0, -5.0, 0.0, 5.0, 10.0)   # degrees
+MOVE_SCALES = (0.9, 1.0, 1.1)
+MOVE_SHIFTS = (-0.2, -0.1, 0.0, 0.1, 0.2)
+
+
+def clip_moves(n, T_out, rng=np.random, coin=random, angle_candidate=MOVE_ANGLES,
+               scale_candidate=MOVE_SCALES, transform_candidate=MOVE_SHIFTS,
+               move_time_candidate=(1,)):
+    """(n,) MOVE_DTYPE: one random move per clip, drawn as ST-GCN's random_move
+    draws it, clip by clip: ``coin.choice(move_time_candidate)`` segments with
+    key nodes at ``arange(0, T_out, T_out / move_time).round()`` and at T_out
+    (frames 0 and T_out by default), then ``rng.choice`` of one angle (degrees;
+    stored in radians, ``* np.pi / 180``), one scale, one x and one y translation
+    per node, in that order. At most 3 segments (4 nodes)."""
+    out = np.zeros(n, dtype=MOVE_DTYPE)
+    for i in range(n):
+        move_time = coin.choice(move_time_candidate)
+        node = np.append(np.arange(0, T_out, T_out * 1.0 / move_time).round().astype(int), T_out)
+        k = len(node)
+        if not 2 <= k <= 4 or np.any(np.diff(node) <= 0):
+            raise ValueError(f"clip_moves: {move_time} segments over {T_out} frames give the "
+                             f"nodes {node.tolist()}: 2 to 4 strictly increasing frames needed")
+        out["nk"][i] = k
+        out["frame"][i, :k] = node
+        out["angle"][i, :k] = rng.choice(angle_candidate, k) * np.pi / 180
+        out["scale"][i, :k] = rng.choice(scale_candidate, k)
+        out["tx"][i, :k] = rng.choice(transform_candidate, k)
+        out["ty"][i, :k] = rng.choice(transform_candidate, k)
+    return out
+
+
+def move_is_valid(mv, T_out):
+    """What the kernel accepts of one MOVE_DTYPE record: nk = 0, or 2..4 nodes
+    with frame[0] = 0, strictly increasing frames, the last at T_out - 1 or
+    later, and finite parameters."""
+    nk = int(mv["nk"])
+    if nk == 0:
+        return True
+    if not 2 <= nk <= 4:
+        return False
+    f = mv["frame"][:nk].astype(np.int64)
+    return bool(f[0] == 0 and np.all(np.diff(f) > 0) and f[-1] >= T_out - 1 and
+                all(np.isfinite(mv[p][:nk]).all() for p in ("angle", "scale", "tx", "ty")))
+
+
+def move_frame_affine(moves, T_out):
+    """(N, 4, T_out) float64 [c, sn, tx, ty] of every frame, by the kernel's
+    arithmetic: frame t in segment k (frame[k] <= t < frame[k + 1], the last
+    frame in the last segment), every parameter p(t) = p_k + (t - f_k) *
+    ((p_{k+1} - p_k) / (f_{k+1} - f_k)) (np.linspace's start + i * step), then
+    c = cos(a) * s, sn = sin(a) * s. nk = 0 gives [1, 0, 0, 0]."""
+    out = np.zeros((len(moves), 4, T_out))
+    out[:, 0] = 1.0
+    t = np.arange(T_out)
+    for n, mv in enumerate(moves):
+        nk = int(mv["nk"])
+        if nk == 0:
+            continue
+        if not move_is_valid(mv, T_out):
+            raise ValueError(f"move_frame_affine: record {n} is invalid for {T_out} frames")
+        f = mv["frame"][:nk].astype(np.int64)
+        k = np.clip(np.searchsorted(f, t, side="right") - 1, 0, nk - 2)
+        i, span = (t - f[k]).astype(np.float64), (f[k + 1] - f[k]).astype(np.float64)
+        a, s, tx, ty = (mv[p][k] + i * ((mv[p][k + 1] - mv[p][k]) / span)
+                        for p in ("angle", "scale", "tx", "ty"))
+        out[n] = np.cos(a) * s, np.sin(a) * s, tx, ty
+    return out
+
+
+def apply_moves_reference(x_ntvc, moves):
+    """The move kernel's arithmetic in numpy float64 (the CPU yardstick of
+    stgcn_input_stage_move): x_ntvc (N, T, V, C >= 2) -> float64 of that shape
+    with x' = (c x - sn y) + tx, y' = (sn x + c y) + ty per frame
+    (``move_frame_affine``), every operation rounded on its own; further channels
+    and the clips with nk = 0 unchanged."""
+    out = np.array(x_ntvc, dtype=np.float64)
+    aff = move_frame_affine(moves, out.shape[1])
+    for n, mv in enumerate(moves):
+        if int(mv["nk"]) == 0:
+            continue
+        c, sn, tx, ty = (q[:, None] for q in aff[n])
+        px, py = out[n, :, :, 0].copy(), out[n, :, :, 1].copy()
+        out[n, :, :, 0] = (c * px - sn * py) + tx
+        out[n, :, :, 1] = (sn * px + c * py) + ty
+    return out
+
+
 def _np_dtype(dtype):
     if isinstance(dtype, torch.dtype):
         dtype = {torch.float32: np.float32, torch.float64: np.float64}.get(dtype, dtype)
@@ -221,7 +318,8 @@ def _np_dtype(dtype):
     return dtype
 
 
-def pack_clips(items, T_out, C_src, dtype, out=None, transforms=None):
+def pack_clips(items, T_out, C_src, dtype, out=None, transforms=None, crop="first",
+               coin=random):
     """items: [(clip (T_i, V, C_src) or (1, T_i, V, C_src), label), ...] ->
     (staging (frames, V, C_src) of ``dtype``, table (N,) CLIP_DTYPE, labels (N,)
     int64). The first min(T_i, T_out) frames of every clip lie back to back in
@@ -230,8 +328,13 @@ def pack_clips(items, T_out, C_src, dtype, out=None, transforms=None):
     (N, 2, 2) matrices (``clip_transforms``); an identity, or None, gives
     flags = 0 (the kernel's plain cast). out: a float array or CPU tensor of
     ``dtype`` to pack into (pinned memory, for an asynchronous copy) with room
-    for the frames: N * T_out frames always suffice. Without it a new array."""
+    for the frames: N * T_out frames always suffice. Without it a new array.
+    crop="random": a clip with T_i > T_out gives the T_out frames from
+    ``coin.randint(0, T_i - T_out)`` on (ST-GCN's "random choose"), drawn clip by
+    clip in item order; nothing is drawn for a clip that fits."""
     dtype = _np_dtype(dtype)
+    if crop not in ("first", "random"):
+        raise ValueError(f"pack_clips: crop is 'first' or 'random', not {crop!r}")
     clips = []
     for x, _ in items:
         x = np.asarray(x)
@@ -263,7 +366,8 @@ def pack_clips(items, T_out, C_src, dtype, out=None, transforms=None):
     table["m"] = (1.0, 0.0, 0.0, 1.0)
     first = 0
     for i, (c, f) in enumerate(zip(clips, frames)):
-        buf[first:first + f] = c[:f]
+        start = coin.randint(0, c.shape[0] - f) if crop == "random" and c.shape[0] > f else 0
+        buf[first:first + f] = c[start:start + f]
         table["first_frame"][i], table["frames"][i] = first, f
         first += f
     if transforms is not None:
@@ -280,14 +384,18 @@ def pack_clips(items, T_out, C_src, dtype, out=None, transforms=None):
     return buf, table, labels
 
 
-def stage_clips(src, table, x, status):
+def stage_clips(src, table, x, status, moves=None):
     """One stgcn_input_stage launch on the current stream: src (frames, V,
     C_src) fp32 / fp64 on the device (its first dimension is the capacity the
     kernel checks the table against), table the device copy of a CLIP_DTYPE
     table (any dtype, N * 48 bytes), x (N, C, T_out, V) fp32 written in full,
     status (N,) int32 written in full: 1 where the clip's entry was invalid
     (that clip is zeros). The table is read when the kernel runs: inside a
-    captured graph, rewrite src and the table between replays. Returns x."""
+    captured graph, rewrite src and the table between replays. Returns x.
+    moves: the device copy of a MOVE_DTYPE table (any dtype, N * 160 bytes, read
+    when the kernel runs like the clip table): the launch is
+    stgcn_input_stage_move, which applies each clip's move after its matrix; an
+    invalid record adds 2 to status[n] and zeros the clip."""
     if x.dtype != torch.float32 or x.dim() != 4 or not x.is_contiguous():
         raise ValueError("stage_clips: x is a contiguous (N, C, T_out, V) float32 tensor")
     N, C, T_out, V = x.shape
@@ -303,8 +411,17 @@ def stage_clips(src, table, x, status):
         raise ValueError("stage_clips: src, table, x and status live on one GPU")
     d = hip_lib.InputDesc(N, C, T_out, V, src.shape[2], int(src.dtype == torch.float64),
                           src.shape[0])
-    hip_lib.check(hip_lib.lib().stgcn_input_stage(
-        ctypes.byref(d), hip_lib.ptr(src), hip_lib.ptr(table), hip_lib.ptr(x),
+    if moves is None:
+        hip_lib.check(hip_lib.lib().stgcn_input_stage(
+            ctypes.byref(d), hip_lib.ptr(src), hip_lib.ptr(table), hip_lib.ptr(x),
+            hip_lib.ptr(status), hip_lib.stream_handle(x.device)))
+        return x
+    if not moves.is_contiguous() or moves.device != x.device or \
+            moves.numel() * moves.element_size() < N * MOVE_DTYPE.itemsize:
+        raise ValueError(f"stage_clips: moves needs {N * MOVE_DTYPE.itemsize} contiguous bytes "
+                         "on x's GPU")
+    hip_lib.check(hip_lib.lib().stgcn_input_stage_move(
+        ctypes.byref(d), hip_lib.ptr(src), hip_lib.ptr(table), hip_lib.ptr(moves), hip_lib.ptr(x),
         hip_lib.ptr(status), hip_lib.stream_handle(x.device)))
     return x
 
@@ -336,11 +453,24 @@ class RaggedDeviceLoader:
     written into and that are yielded themselves, e.g. the inputs a GraphedStep
     captured; each batch then has out.shape[0] clips. An invalid table entry
     (there is none unless the packing is broken) raises once, after the last
-    batch, from one host read."""
+    batch, from one host read.
+
+    move=True: one random move per clip (``clip_moves`` over the batch's T_out,
+    python's random and np.random) applied by the kernel after the clip's
+    matrix (stgcn_input_stage_move); the records travel behind the clip table
+    in the slot's table staging, under the same events. crop="random": a clip
+    longer than T_out gives a random window instead of its first T_out frames
+    (``pack_clips``). Per batch the draws are: the matrices, the moves, the
+    window starts. An invalid move record is reported like an invalid table
+    entry, once, after the last batch."""
 
     def __init__(self, batches_of_items, device, V, C, C_src, T_out=None,
-                 src_dtype=torch.float32, augment=False, out=None, labels_out=None):
+                 src_dtype=torch.float32, augment=False, out=None, labels_out=None,
+                 move=False, crop="first"):
         self.batches, self.device = batches_of_items, torch.device(device)
+        if crop not in ("first", "random"):
+            raise ValueError(f"RaggedDeviceLoader: crop is 'first' or 'random', not {crop!r}")
+        self.move, self.crop = bool(move), crop
         self.V, self.C, self.C_src, self.T_out = V, C, C_src, T_out
         self.src_dtype, self.augment = src_dtype, augment
         self.np_dtype = _np_dtype(src_dtype)
@@ -353,7 +483,8 @@ class RaggedDeviceLoader:
                              "float32 tensor")
         d = hip_lib.InputDesc(1, C, T_out or 1, V, C_src, int(src_dtype == torch.float64), 1)
         lib = hip_lib.load_library()
-        if lib.stgcn_input_check(ctypes.byref(d)) != 0:
+        check = lib.stgcn_input_move_check if self.move else lib.stgcn_input_check
+        if check(ctypes.byref(d)) != 0:
             raise ValueError("RaggedDeviceLoader: " +
                              lib.stgcn_last_error().decode(errors="replace"))
         self.stream = torch.cuda.Stream(self.device)
@@ -374,17 +505,21 @@ class RaggedDeviceLoader:
             slot.host = torch.empty(need, dtype=self.src_dtype).pin_memory()
             with torch.cuda.stream(self.stream):
                 slot.dev = torch.empty(need, dtype=self.src_dtype, device=self.device)
-        nb = N * CLIP_DTYPE.itemsize
+        nc = N * CLIP_DTYPE.itemsize   # (a multiple of 16: the records behind it are aligned)
+        nb = nc + (N * MOVE_DTYPE.itemsize if self.move else 0)
         if slot.host_table is None or slot.host_table.numel() < nb:
             slot.host_table = torch.empty(nb, dtype=torch.uint8).pin_memory()
             with torch.cuda.stream(self.stream):
                 slot.dev_table = torch.empty(nb, dtype=torch.uint8, device=self.device)
         tr = clip_transforms(N, True) if self.augment else None
+        mv = clip_moves(N, T_out) if self.move else None
         buf, table, labels = pack_clips(items, T_out, self.C_src, self.np_dtype, out=slot.host,
-                                        transforms=tr)
+                                        transforms=tr, crop=self.crop)
         if buf.shape[1] != self.V:
             raise ValueError(f"RaggedDeviceLoader: clips of {buf.shape[1]} joints, V = {self.V}")
-        slot.host_table.numpy()[:nb] = table.view(np.uint8)
+        slot.host_table.numpy()[:nc] = table.view(np.uint8)
+        if mv is not None:
+            slot.host_table.numpy()[nc:nb] = mv.view(np.uint8)
         yh = torch.from_numpy(labels).pin_memory()
         with torch.cuda.stream(self.stream):
             if slot.free is not None:
@@ -426,7 +561,10 @@ class RaggedDeviceLoader:
             status = torch.empty(N, dtype=torch.int32, device=self.device)
             cap = slot.dev.numel() // (self.V * self.C_src)
             src = slot.dev[:cap * self.V * self.C_src].view(cap, self.V, self.C_src)
-            stage_clips(src, slot.dev_table, x, status)
+            nc = N * CLIP_DTYPE.itemsize
+            stage_clips(src, slot.dev_table, x, status,
+                        moves=slot.dev_table[nc:nc + N * MOVE_DTYPE.itemsize] if self.move
+                        else None)
             slot.free = torch.cuda.Event()
             slot.free.record(cur)
             statuses.append(status)
@@ -434,8 +572,10 @@ class RaggedDeviceLoader:
                 self.labels_out.copy_(yd)
                 yd = self.labels_out
             yield x, yd
-        bad = torch.cat(statuses).nonzero().flatten().tolist()  # (the one host read)
-        if bad:
-            raise RuntimeError(f"RaggedDeviceLoader: invalid clip table entries (flat clip "
-                               f"indices {bad[:8]}{' ...' if len(bad) > 8 else ''}): those "
-                               "clips were staged as zeros")
+        flags = torch.cat(statuses).cpu()  # (the one host read)
+        for bit, what in ((1, "clip table entries"), (2, "move records")):
+            bad = (flags & bit).nonzero().flatten().tolist()
+            if bad:
+                raise RuntimeError(f"RaggedDeviceLoader: invalid {what} (flat clip "
+                                   f"indices {bad[:8]}{' ...' if len(bad) > 8 else ''}): those "
+                                   "clips were staged as zeros")

@@ -39,6 +39,7 @@ FEATURE_STEP_STATE = 4  # per-step values from device memory (dropout token, lr,
 FEATURE_INPUT_STAGE = 8  # stgcn_input_check / stgcn_input_stage (data.stage_clips)
 FEATURE_OPTIMIZERS = 16  # stgcn_opt_*: AdamW, AMSGrad (train_ops.FusedAdam / FusedAdamW)
 FEATURE_HEAD_LOSS = 32  # stgcn_loss_check, stgcn_head_eval_loss / _u (train_ops.head_eval)
+FEATURE_INPUT_MOVE = 64  # stgcn_input_move_check / stgcn_input_stage_move (data.clip_moves)
 LOSS_WEIGHT = 1  # stgcn_loss_desc_t.flags: class_weight is given
 OPT_ADAM = 1  # stgcn_opt_desc_t.algo
 OPT_DECOUPLED_WD, OPT_AMSGRAD = 2, 4  # stgcn_opt_desc_t.flags
@@ -142,6 +143,15 @@ class Clip(ctypes.Structure):  # stgcn_clip_t, 48 bytes (numpy: data.CLIP_DTYPE)
                 ("m", ctypes.c_double * 4)]
 
 
+class Move(ctypes.Structure):  # stgcn_move_t, 160 bytes (numpy: data.MOVE_DTYPE)
+    _fields_ = [("nk", _c_int), ("frame", _c_int * 4), ("reserved0", _c_int),
+                ("angle", ctypes.c_double * 4), ("scale", ctypes.c_double * 4),
+                ("tx", ctypes.c_double * 4), ("ty", ctypes.c_double * 4),
+                ("reserved1", ctypes.c_int64)]
+
+
+assert ctypes.sizeof(Move) == 160 and Move.angle.offset == 24 and Move.ty.offset == 120
+
 # Every symbol include/stgcn_hip.h declares (checked by tests/test_capi.py).
 EXPORTED = ("stgcn_abi_version", "stgcn_last_error", "stgcn_check_desc",
             "stgcn_fwd_workspace_bytes", "stgcn_bwd_workspace_bytes",
@@ -156,7 +166,8 @@ EXPORTED = ("stgcn_abi_version", "stgcn_last_error", "stgcn_check_desc",
             "stgcn_seed_next", "stgcn_adam_step_dev2", "stgcn_grad_norm_bytes",
             "stgcn_grad_norm", "stgcn_input_check", "stgcn_input_stage", "stgcn_opt_check",
             "stgcn_opt_table_bytes", "stgcn_opt_build_table", "stgcn_opt_step",
-            "stgcn_loss_check", "stgcn_head_eval_loss", "stgcn_head_eval_loss_u")
+            "stgcn_loss_check", "stgcn_head_eval_loss", "stgcn_head_eval_loss_u",
+            "stgcn_input_move_check", "stgcn_input_stage_move")
 
 _LIB = None
 
@@ -268,6 +279,10 @@ def load_library(path=LIB_PATH):
     lib.stgcn_input_check.restype = ctypes.c_int
     lib.stgcn_input_stage.argtypes = [ctypes.POINTER(InputDesc), _vp, _vp, _vp, _vp, _vp]
     lib.stgcn_input_stage.restype = ctypes.c_int
+    lib.stgcn_input_move_check.argtypes = [ctypes.POINTER(InputDesc)]
+    lib.stgcn_input_move_check.restype = ctypes.c_int
+    lib.stgcn_input_stage_move.argtypes = [ctypes.POINTER(InputDesc), _vp, _vp, _vp, _vp, _vp, _vp]
+    lib.stgcn_input_stage_move.restype = ctypes.c_int
     if lib.stgcn_abi_version() != ABI_VERSION:
         raise RuntimeError("libstgcn_hip.so ABI version mismatch; rebuild it")
     return lib
