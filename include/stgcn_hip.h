@@ -67,8 +67,18 @@
  *     Wt is (C_out, C_out, 9) (the (9,1) Conv2d weight).
  *   - The workspace is caller-allocated (query *_workspace_bytes first); the
  *     library allocates nothing on the hot path and keeps no mutable global
- *     state besides the thread-local error string.
- *   - Every launch goes on the caller's stream (a hipStream_t passed as void*).
+ *     state besides the thread-local error string (and the internal stream of
+ *     the next point).
+ *   - Every launch goes on the caller's stream (a hipStream_t passed as void*),
+ *     with one exception: stgcn_block_bwd / _bwd_dseed may run part of its work
+ *     on an internal stream that is forked from the caller's stream and joined
+ *     to it within the call (STGCN_FEATURE_BWD_OVERLAP; stgcn_bwd_overlap(0)
+ *     keeps every launch on the caller's). To
+ *     the caller nothing changes: when the call returns, everything it enqueued
+ *     is ordered before later work on the caller's stream, under stream capture
+ *     too (the captured graph then has two parallel branches per such block).
+ *     The library's only other process-wide state is that stream with its
+ *     events and the mode of stgcn_bwd_overlap.
  *   - Return 0 on success, a negative STGCN_E* code otherwise; the message is
  *     in stgcn_last_error() (thread-local).
  */
@@ -308,7 +318,25 @@ const char *stgcn_last_error(void);
 #define STGCN_FEATURE_INPUT_MOVE 64 /* stgcn_input_move_check / stgcn_input_stage_move:
                                     * per-frame interpolated rotation, scale and translation
                                     * ("random moving") in the input stage              */
+#define STGCN_FEATURE_BWD_OVERLAP 128 /* stgcn_bwd_overlap: the backward's small kernels on an
+                                    * internal stream beside its GEMMs                   */
 int stgcn_features(void);
+
+/* STGCN_FEATURE_BWD_OVERLAP: stgcn_block_bwd / _bwd_dseed of a folded block whose
+ * SpatialConv backward is fused into its data gradient (STGCN_PLAN_FOLD with
+ * STGCN_PLAN_SP_BWD_FUSED) may run its small reduction kernels on a stream the
+ * library owns (one per device, created by the first such call that is not under
+ * stream capture; a call that is captured earlier runs serially), forked from the
+ * caller's stream after the ReLU + BN2 backward pass and joined to it before the
+ * call returns: the same kernels with the same launch parameters and the same
+ * order between any two that touch the same buffer, so the results have the
+ * serial call's bits. Sets the process-wide mode (1: on, the default; 0: every
+ * launch on the caller's stream -- for an application that must keep all work
+ * on its own stream, and for comparing the two) and returns the previous one; a
+ * negative argument only queries. The stream has the default priority: a
+ * high-priority one made the captured step much slower (DESIGN.md "Backward
+ * small kernels beside the GEMMs"). */
+int stgcn_bwd_overlap(int enable);
 
 /* Validate a descriptor without touching the GPU (0 = supported). */
 int stgcn_check_desc(const stgcn_desc_t *d);

@@ -13,7 +13,9 @@ from collections import defaultdict
 
 def main(path, steps=10):
     rows = sorted(csv.DictReader(open(path)), key=lambda r: int(r["Start_Timestamp"]))
-    adam = [i for i, r in enumerate(rows) if "adam" in r["Kernel_Name"].lower()]
+    # (the device-step Adam launches k_adam_tick first: one delimiter per step)
+    adam = [i for i, r in enumerate(rows) if "adam" in r["Kernel_Name"].lower()
+            and "adam_tick" not in r["Kernel_Name"]]
     seg = rows[adam[-steps - 1] + 1: adam[-1] + 1]
     t0, t1 = int(seg[0]["Start_Timestamp"]), int(seg[-1]["End_Timestamp"])
     busy, cs, ce = 0, None, None
@@ -26,9 +28,11 @@ def main(path, steps=10):
         else:
             ce = max(ce, e)
     busy += ce - cs
+    # (summed kernel time above the busy time: kernels ran beside each other)
+    ksum = sum(int(r["End_Timestamp"]) - int(r["Start_Timestamp"]) for r in seg)
     print(f"steps {steps}: wall {(t1 - t0) / 1e6 / steps:.3f} ms/step, GPU busy "
-          f"{busy / 1e6 / steps:.3f} ms/step ({busy / (t1 - t0):.4f}), "
-          f"{len(seg) / steps:.0f} launches/step")
+          f"{busy / 1e6 / steps:.3f} ms/step ({busy / (t1 - t0):.4f}), summed kernel time "
+          f"{ksum / 1e6 / steps:.3f} ms/step, {len(seg) / steps:.0f} launches/step")
     agg, cnt = defaultdict(float), defaultdict(int)
     for r in seg:
         name = r["Kernel_Name"].replace("(anonymous namespace)::", "")

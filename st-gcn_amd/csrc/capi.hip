@@ -1,7 +1,9 @@
 // C-ABI entry points of libstgcn_hip.so (declared in include/stgcn_hip.h).
 //
 // stgcn_block_fwd / stgcn_block_bwd enqueue the kernel sequence of one
-// ST-GCN block on the caller's stream. The reference op order of the default
+// ST-GCN block on the caller's stream (the fused folded backward: its small
+// kernels on a side stream forked from and joined to it, BwdCtx::fk). The
+// reference op order of the default
 // (non-residual) block
 // (st_graphconv.py:97-109, :148-150) is
 //     BN1 -> Y = W x + b -> Z = sum_k Y_k A_k^T -> Conv9x1 -> BN2 -> ReLU;
@@ -552,6 +554,13 @@ struct BwdCtx {
   double *tqT;
   PrevBn pvb;        // defer: the previous block's BN2, the chain sums s1 / s2
   const float *xin;  // defer: the previous block's U in place of x
+  // The fused folded block (fold_spb): its small kernels run on the library's
+  // side stream beside the data- and weight-gradient GEMMs (host_common.h
+  // SideFork; DESIGN.md "Backward small kernels beside the GEMMs"). Not forked:
+  // side() == s, and the stages below are the serial sequence.
+  bool overlap;
+  SideFork fk;
+  hipStream_t side() const { return fk.forked() ? fk.side() : s; }
 };
 
 int bwd_check_args(const stgcn_desc_t *d, const stgcn_bwd_args_t *a, void *workspace) {
@@ -643,14 +652,17 @@ int bwd_relu_bn2(BwdCtx &c) {
                                             du_bf16(d) ? 1 : 0, a->dy_coef, L.fcs,
                                             f16x2_tw(d) ? L.amax : nullptr,  // (f16x2: max |dU|)
                                             a->dy_nc));
+    // (fork: the small kernels from here to launch_chain_coef need the apply
+    // pass's sums, never the GEMMs' tensors)
+    if (c.overlap) HIP_TRY(c.fk.begin(s));
     HIP_TRY(launch_fold_tq(L.fcs, apply_cols_chunks(N), R, T, To, V, d->stride, L.ftq, c.tqT,
-                           s));
+                           c.side()));
   } else {
     HIP_TRY(launch_bn_relu_bwd_apply(a->dy, a->U, c.mean2, c.invstd2, a->g2, a->b2, sg, sgu, L.dU,
                                      L.sdu, N, R, To * V, d->training, drop, s,
                                      du_bf16(d) ? 1 : 0, a->dy_coef, a->dy_nc));
   }
-  HIP_TRY(launch_bn_grads_out(sg, sgu, L.sdu, R, a->dg2, a->db2, a->dbWt, s));
+  HIP_TRY(launch_bn_grads_out(sg, sgu, L.sdu, R, a->dg2, a->db2, a->dbWt, c.side()));
   return STGCN_OK;
 }
 
@@ -683,11 +695,16 @@ int bwd_fold_temporal(BwdCtx &c) {
     }
     HIP_TRY(launch_bias_rv(a->A, a->bW, L.bZ, K, R, V, s));
     HIP_TRY(launch_fold_prep_bwd(a->Wt, a->W, R, C, L.fscr, s));
+    HIP_TRY(c.fk.to_side());  // (forked: launch_fold_sdz reads this Wc)
   }
   if (fold_spb(d)) {  // dbW and the bias part of dA first: the data gradient adds to dA;
     // BN1's sd from the dU sums (fp64, exact against the cancellation in sum dxhat)
-    HIP_TRY(launch_fold_sdz(f64scr, a->Wt, Wc, L.ftq, R, C, V, L.SdZ, L.SdH, s, pre, c.tqT));
-    HIP_TRY(launch_fold_small_sd(L.SdZ, a->A, a->bW, R, V, a->dbW, a->dA, L.SdH, C, L.sd, s));
+    // (forked: beside the data gradient, which with sd_given and partial slots
+    // touches neither sd nor dA; launch_dA_reduce follows on the same stream)
+    HIP_TRY(launch_fold_sdz(f64scr, a->Wt, Wc, L.ftq, R, C, V, L.SdZ, L.SdH, c.side(), pre,
+                            c.tqT));
+    HIP_TRY(launch_fold_small_sd(L.SdZ, a->A, a->bW, R, V, a->dbW, a->dA, L.SdH, C, L.sd,
+                                 c.side()));
   }
   if (f16x2_dgrad(d) && !pre)  // the fp16 splits' operand scales: max |dU| (apply pass), max |Wc|
     HIP_TRY(launch_absmax(Wc, (int64_t)R * C * 9, L.amax + kAmaxWords, s));
@@ -732,9 +749,13 @@ int bwd_fold_temporal(BwdCtx &c) {
         p.wpk_ready = 1;
       }
       dA_slots(p);
+      // (no slots: the launch's atomics into dA must follow launch_fold_small_sd's
+      // store -- joined here, the call is serial from this launch on)
+      if (!p.dA_part) HIP_TRY(c.fk.join());
       HIP_TRY(launch_conv_gemm(p, s));
     }
-    HIP_TRY(launch_dA_reduce(L.dApart, dparts, V * V, L.dAlvl, a->dA, s));
+    HIP_TRY(c.fk.to_side());  // (forked: the partials, and chain_coef's sdn / s1 / s2)
+    HIP_TRY(launch_dA_reduce(L.dApart, dparts, V * V, L.dAlvl, a->dA, c.side()));
   }
   WgradParams w;
   if (fold_bna(d)) {  // dWc = sum (dU A) BN1(x): Q = x with BN1 at staging, P = dU A
@@ -769,6 +790,7 @@ int bwd_fold_temporal(BwdCtx &c) {
     }
   }
   HIP_TRY(launch_wgrad_taps(w, s));
+  HIP_TRY(c.fk.to_main());  // (forked: Tq, and whatever a serial tail reads, is on the side stream)
   HIP_TRY(launch_fold_grads(L.slab, w.S, fscr, bZ, L.ftq, R, C, V, L.dWc, a->dWt, a->dW, s));
   return STGCN_OK;
 }
@@ -909,9 +931,10 @@ int bwd_bn1_tail(BwdCtx &c) {
   const BwdLayout &L = c.L;
   hipStream_t s = c.s;
   const int N = d->N, C = d->C_in, R = d->C_out, T = d->T, V = d->V;
-  if (c.defer) {
+  if (c.defer) {  // (forked: after launch_dA_reduce on the side stream, beside launch_fold_grads)
     HIP_TRY(launch_chain_coef(L.sd, L.sdn, c.mean1, c.invstd1, a->g1, L.s1, L.s2, a->x_stats, C,
-                              (int64_t)N * T * V, a->dg1, a->db1, a->dx_coef, a->prev_sums, s));
+                              (int64_t)N * T * V, a->dg1, a->db1, a->dx_coef, a->prev_sums,
+                              c.side()));
     return STGCN_OK;
   }
   HIP_TRY(launch_bn_grads_out(L.sd, L.sdn, nullptr, C, a->dg1, a->db1, nullptr, s));
@@ -980,6 +1003,8 @@ extern "C" int stgcn_block_bwd_dseed(const stgcn_desc_t *d, const stgcn_bwd_args
   }
   c.xin = c.defer ? a->prev_U : a->x;
   if (cols_sums(d)) c.tqT = fold_sdz_tq_slot(c.L.f64scr, R, C);
+  // (every other path -- unfolded, bf16 / K = 3 spatial backward, residual -- is serial)
+  c.overlap = fold_w(d) && fold_spb(d) && !c.res && cols_sums(d);
 
   HIP_TRY(hipMemsetAsync(workspace, 0, c.L.dbl_bytes, c.s));
   STAGE(bwd_relu_bn2(c));
@@ -991,7 +1016,16 @@ extern "C" int stgcn_block_bwd_dseed(const stgcn_desc_t *d, const stgcn_bwd_args
     STAGE(bwd_spatial_wgrad(c));
   }
   STAGE(bwd_spatial_dgrad(c));
-  return bwd_bn1_tail(c);
+  STAGE(bwd_bn1_tail(c));
+  // (forked: the caller's stream waits for the side stream's last kernel, so the
+  // call returns as a serial one does; on an error above c's destructor joins)
+  HIP_TRY(c.fk.join());
+  return STGCN_OK;
+}
+
+extern "C" int stgcn_bwd_overlap(int enable) {
+  std::atomic<int> &mode = bwd_overlap_mode();
+  return enable < 0 ? mode.load() : mode.exchange(enable ? 1 : 0);
 }
 
 // ---------------------------------------------------------------------------

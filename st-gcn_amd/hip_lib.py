@@ -40,6 +40,7 @@ FEATURE_INPUT_STAGE = 8  # stgcn_input_check / stgcn_input_stage (data.stage_cli
 FEATURE_OPTIMIZERS = 16  # stgcn_opt_*: AdamW, AMSGrad (train_ops.FusedAdam / FusedAdamW)
 FEATURE_HEAD_LOSS = 32  # stgcn_loss_check, stgcn_head_eval_loss / _u (train_ops.head_eval)
 FEATURE_INPUT_MOVE = 64  # stgcn_input_move_check / stgcn_input_stage_move (data.clip_moves)
+FEATURE_BWD_OVERLAP = 128  # stgcn_bwd_overlap: the backward's small kernels beside its GEMMs
 LOSS_WEIGHT = 1  # stgcn_loss_desc_t.flags: class_weight is given
 OPT_ADAM = 1  # stgcn_opt_desc_t.algo
 OPT_DECOUPLED_WD, OPT_AMSGRAD = 2, 4  # stgcn_opt_desc_t.flags
@@ -167,7 +168,7 @@ EXPORTED = ("stgcn_abi_version", "stgcn_last_error", "stgcn_check_desc",
             "stgcn_grad_norm", "stgcn_input_check", "stgcn_input_stage", "stgcn_opt_check",
             "stgcn_opt_table_bytes", "stgcn_opt_build_table", "stgcn_opt_step",
             "stgcn_loss_check", "stgcn_head_eval_loss", "stgcn_head_eval_loss_u",
-            "stgcn_input_move_check", "stgcn_input_stage_move")
+            "stgcn_input_move_check", "stgcn_input_stage_move", "stgcn_bwd_overlap")
 
 _LIB = None
 
@@ -283,6 +284,8 @@ def load_library(path=LIB_PATH):
     lib.stgcn_input_move_check.restype = ctypes.c_int
     lib.stgcn_input_stage_move.argtypes = [ctypes.POINTER(InputDesc), _vp, _vp, _vp, _vp, _vp, _vp]
     lib.stgcn_input_stage_move.restype = ctypes.c_int
+    lib.stgcn_bwd_overlap.argtypes = [ctypes.c_int]
+    lib.stgcn_bwd_overlap.restype = ctypes.c_int
     if lib.stgcn_abi_version() != ABI_VERSION:
         raise RuntimeError("libstgcn_hip.so ABI version mismatch; rebuild it")
     return lib
