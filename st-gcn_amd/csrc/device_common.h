@@ -5,12 +5,14 @@
 // resources, LDS-DMA and the explicit waits (first half of this file), then the
 // reductions and the conv tile epilogues. A kernel file keeps a variant of its
 // own only where the variant's point is what differs (e.g. a wait that names
-// the staging registers it protects).
+// the staging registers it protects). The numerics that several kernels must
+// agree on, the BatchNorm / ReLU element math, have their home in bn_math.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
 
+#include "bn_math.h"
 #include "internal.h"
 
 

@@ -82,9 +82,9 @@ __global__ __launch_bounds__(256) void k_gather_fwd(const float *x, const float 
   for (int ci = 0; ci < C; ++ci) {
     __syncthreads();
     const float *src = x + ((int64_t)n * C + ci) * L + (int64_t)t0 * V;
-    const float mu = mean[ci], a = invstd[ci] * g[ci], be = b[ci];
+    const BnAff bn = bn_aff(mean, invstd, g, b, ci);
     for (int i = threadIdx.x; i < tc * V; i += 256) {
-      const float t = (src[i] - mu) * a + be;
+      const float t = bn.pre(src[i]);
       xs[i] = relu ? fmaxf(t, 0.f) : t;
     }
     __syncthreads();
@@ -140,12 +140,12 @@ __global__ __launch_bounds__(256) void k_gather3(const float *__restrict__ x,
   const int64_t n = r / CT;
   const int rem = (int)(r - n * CT);
   const int ci = rem / T, t = rem - ci * T;
-  const float mu = mean[ci], a = invstd[ci] * g[ci], be = b[ci];
+  const BnAff bn = bn_aff(mean, invstd, g, b, ci);
   const float *xr = x + r * V;
   float xv[VP];
 #pragma unroll
   for (int w = 0; w < VP; ++w) {
-    const float t = w < V ? (xr[w] - mu) * a + be : 0.f;
+    const float t = w < V ? bn.pre(xr[w]) : 0.f;
     xv[w] = relu ? fmaxf(t, 0.f) : t;
   }
   for (int k = 0; k < K; ++k) {
@@ -218,11 +218,8 @@ __global__ __launch_bounds__(256) void k_gather4(const float *__restrict__ x,
 #pragma unroll
   for (int w = 0; w < VP; ++w) {
     float xx = w < V ? xs[tid * V + w] : 0.f;
-    if (prev) {
-      const float u = (xx - pmu) * pa + pbe;
-      xx = u > 0.f ? u : 0.f;
-    }
-    const float t = w < V ? (xx - mu) * a + be : 0.f;
+    if (prev) xx = bn_relu(bn_pre(xx, pmu, pa, pbe));
+    const float t = w < V ? bn_pre(xx, mu, a, be) : 0.f;
     xv[w] = relu ? fmaxf(t, 0.f) : t;
   }
   for (int k = 0; k < K; ++k) {
@@ -323,8 +320,8 @@ __global__ __launch_bounds__(256) void k_spatial_bwd3(
     float *dxr = dx + r * V;
 #pragma unroll
     for (int w = 0; w < V; ++w) {
-      const float xn = (xv[w] - mu) * is;
-      const float bn = (xv[w] - mu) * a + be;
+      const float xn = bn_hat(xv[w], mu, is);
+      const float bn = bn_pre(xv[w], mu, a, be);
       if (relu && bn <= 0.f) acc[w] = 0.f;  // ReLU'(BN1(x))
       s += acc[w];
       sn = fmaf(acc[w], xn, sn);
@@ -600,10 +597,8 @@ __global__ __launch_bounds__(bwd5_nw(KMAX) * 64) void k_spatial_bwd5(
       const int rem = rem0 + rl;
       const int ci = rem / T;
       const int seg = n0 * C + ci - cfirst;
-      const float mu = mean[ci], is = invstd[ci];
-      const float a = is * g[ci], be = b[ci];
-      // prev mode: the staged plane is the previous block's U; its output x =
-      // ReLU((U - pmu) * pa + pb) as that block's output pass formed it
+      const BnAff bn1 = bn_aff(mean, invstd, g, b, ci);
+      // prev mode: the staged plane is the previous block's U
       const float pmu = pv ? prev.mean[ci] : 0.f, pis = pv ? prev.invstd[ci] : 1.f;
       const float pa = pv ? pis * prev.g[ci] : 1.f, pb = pv ? prev.b[ci] : 0.f;
       float sv[4] = {0.f, 0.f, 0.f, 0.f};
@@ -615,17 +610,17 @@ __global__ __launch_bounds__(bwd5_nw(KMAX) * 64) void k_spatial_bwd5(
           float uh = 0.f;
           bool pm = false;
           if (pv) {
-            const float t = (xv - pmu) * pa + pb;
-            uh = (xv - pmu) * pis;
+            const float t = bn_pre(xv, pmu, pa, pb);
+            uh = bn_hat(xv, pmu, pis);
             pm = t > 0.f;
             xv = pm ? t : 0.f;
           }
           float d = NH == 2 ? dxs[rl * V + w] + dxs2[rl * V + w] : dxs[rl * V + w];
-          const float bn = (xv - mu) * a + be;
+          const float bn = bn1.pre(xv);
           if (relu && bn <= 0.f) d = 0.f;  // ReLU'(BN1(x))
           dxs[rl * V + w] = d;
           sv[0] += d;
-          sv[1] = fmaf(d, (xv - mu) * is, sv[1]);
+          sv[1] = fmaf(d, bn1.hat(xv), sv[1]);
           if (pm) {
             sv[2] += d;
             sv[3] = fmaf(d, uh, sv[3]);
@@ -887,8 +882,7 @@ __global__ __launch_bounds__(512, 1) void k_spatial_bwd6(
       const int rem = rem0 + rl;
       const int ci = rem / T;
       const int seg = n0 * C + ci - cfirst;
-      const float mu = mean[ci], is = invstd[ci];
-      const float a = is * g[ci], be = b[ci];
+      const BnAff bn1 = bn_aff(mean, invstd, g, b, ci);
       const float pmu = pv ? prev.mean[ci] : 0.f, pis = pv ? prev.invstd[ci] : 1.f;
       const float pa = pv ? pis * prev.g[ci] : 1.f, pb = pv ? prev.b[ci] : 0.f;
       float sv[4] = {0.f, 0.f, 0.f, 0.f};
@@ -900,17 +894,17 @@ __global__ __launch_bounds__(512, 1) void k_spatial_bwd6(
           float uh = 0.f;
           bool pm = false;
           if (pv) {  // prev mode: the staged plane is the previous block's U (see bwd5)
-            const float t = (xv - pmu) * pa + pb;
-            uh = (xv - pmu) * pis;
+            const float t = bn_pre(xv, pmu, pa, pb);
+            uh = bn_hat(xv, pmu, pis);
             pm = t > 0.f;
             xv = pm ? t : 0.f;
           }
           float d = dxs[rl * V + w] + dxs2[rl * V + w];
-          const float bn = (xv - mu) * a + be;
+          const float bn = bn1.pre(xv);
           if (relu && bn <= 0.f) d = 0.f;
           dxs[rl * V + w] = d;
           sv[0] += d;
-          sv[1] = fmaf(d, (xv - mu) * is, sv[1]);
+          sv[1] = fmaf(d, bn1.hat(xv), sv[1]);
           if (pm) {
             sv[2] += d;
             sv[3] = fmaf(d, uh, sv[3]);
@@ -1084,12 +1078,12 @@ __global__ __launch_bounds__(256, 2) void k_gather_mfma(
     const int n0 = r0 / CT, rem0 = r0 - n0 * CT;
     const int row = rt * 32 + lo;
     const int ci = (rem0 + row) / T;
-    const float mu = mean[ci], a = invstd[ci] * g[ci], be = b[ci];
+    const BnAff bn = bn_aff(mean, invstd, g, b, ci);
     float fv[VH];
 #pragma unroll
     for (int s2 = 0; s2 < VH; ++s2) {
       const int w = 2 * s2 + hi;
-      const float t = w < V ? (xs[row * V + w] - mu) * a + be : 0.f;
+      const float t = w < V ? bn.pre(xs[row * V + w]) : 0.f;
       fv[s2] = w < V ? (relu ? fmaxf(t, 0.f) : t) : 0.f;
     }
 #pragma unroll
@@ -1357,9 +1351,9 @@ __global__ __launch_bounds__(256) void k_spatial_dx(const float *H, const float 
   for (int ci = 0; ci < C; ++ci) {
     __syncthreads();
     const int64_t xo = ((int64_t)n * C + ci) * L + (int64_t)t0 * V;
-    const float mu = mean[ci], is = invstd[ci], a = is * g[ci], be = b[ci];
+    const BnAff bn = bn_aff(mean, invstd, g, b, ci);
     for (int i = tid; i < tc * V; i += 256) {
-      const float t = (x[xo + i] - mu) * a + be;
+      const float t = bn.pre(x[xo + i]);
       xb[i] = relu ? fmaxf(t, 0.f) : t;
     }
     for (int i = tid; i < K * tc * V; i += 256) {
@@ -1377,8 +1371,8 @@ __global__ __launch_bounds__(256) void k_spatial_dx(const float *H, const float 
         const float *ac = As + k * V * V + w;
         for (int v = 0; v < V; ++v) acc = fmaf(hr[v], ac[v * V], acc);
       }
-      const float xn = (x[xo + o] - mu) * is;
-      if (relu && (x[xo + o] - mu) * a + be <= 0.f) acc = 0.f;  // ReLU'(BN1(x))
+      const float xn = bn.hat(x[xo + o]);
+      if (relu && bn.pre(x[xo + o]) <= 0.f) acc = 0.f;  // ReLU'(BN1(x))
       if (write_dx) dx[xo + o] = acc;
       s += acc;
       sn += (double)acc * xn;

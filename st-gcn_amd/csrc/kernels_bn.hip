@@ -205,7 +205,7 @@ __device__ __forceinline__ void bn_relu_fwd_body(const float *U, const float *me
   __shared__ double red[8];
   drop = dropout_resolve(drop);
   const int c = blockIdx.x, n0 = blockIdx.y * kBnRows, n1 = min(N, n0 + kBnRows);
-  const float mu = mean[c], is = invstd[c], a = is * g[c], be = b[c];
+  const BnAff bn = bn_aff(mean, invstd, g, b, c);
   double s = 0.0, q = 0.0, cnt = 0.0, su = 0.0, xu = 0.0;
   float ym = 0.f;  // max y (y >= 0): the next block's fp16 operand bound
   // (two vectors' loads issued before either's math; the sums stay fp64 per
@@ -213,17 +213,16 @@ __device__ __forceinline__ void bn_relu_fwd_body(const float *U, const float *me
   auto vec = [&](int64_t base, int i, float (&v)[VEC]) __attribute__((always_inline)) {
 #pragma unroll
     for (int j = 0; j < VEC; ++j) {
-      const float uh = (v[j] - mu) * is;
-      const float t = (v[j] - mu) * a + be;
-      v[j] = t > 0.f ? t : 0.f;
+      const BnReluX e = bn_relu_x(bn, v[j]);
+      v[j] = e.x;
       if (drop.thresh) v[j] = dropout_keep(drop, base + i + j) ? v[j] * drop.scale : 0.f;
       s += (double)v[j];
       q += (double)v[j] * (double)v[j];
       ym = fmaxf(ym, v[j]);
-      if (yext && t > 0.f) {
+      if (yext && e.m) {
         cnt += 1.0;
-        su += (double)uh;
-        xu += (double)v[j] * (double)uh;
+        su += (double)e.uh;
+        xu += (double)v[j] * (double)e.uh;
       }
     }
     if constexpr (WY) vst<VEC>(y + base + i, v);
@@ -297,7 +296,7 @@ __global__ __launch_bounds__(256) void k_bn_relu_bwd_reduce(const float *dy, con
   __shared__ double red[8];
   const int c = blockIdx.x, n = blockIdx.y;
   const int64_t base = ((int64_t)n * C + c) * L;
-  const float mu = mean[c], is = invstd[c], a = is * g[c], be = b[c];
+  const BnAff bn = bn_aff(mean, invstd, g, b, c);
   const float dv = dync ? dync[(int64_t)n * C + c] : 0.f;  // (ABI 10: dy constant per row)
   drop = dropout_resolve(drop);
   double s = 0.0, q = 0.0;
@@ -316,12 +315,11 @@ __global__ __launch_bounds__(256) void k_bn_relu_bwd_reduce(const float *dy, con
         d[j] = dropout_keep(drop, base + i + j) ? d[j] * drop.scale : 0.f;
     }
 #pragma unroll
-    for (int j = 0; j < VEC; ++j) {
-      if ((u[j] - mu) * a + be > 0.f) {
+    for (int j = 0; j < VEC; ++j)
+      if (bn.pre(u[j]) > 0.f) {
         s += d[j];
-        q += (double)d[j] * (double)((u[j] - mu) * is);
+        q += (double)d[j] * (double)bn.hat(u[j]);
       }
-    }
   }
   block_sum2_atomic<256>(s, q, sg + c, sgu + c, red);
 }
@@ -335,6 +333,23 @@ hipError_t launch_bn_relu_bwd_reduce(const float *dy, const float *U, const floa
   return hipGetLastError();
 }
 
+// dU stored as bf16 in the fp32 buffer (its readers round it to bf16 anyway). A
+// macro: behind a call the address arithmetic of one of its two kernels moves.
+#define STGCN_STORE_DU_BF16(dU, base, i, o)                                                  \
+  do {                                                                                       \
+    __bf16 *ob_ = reinterpret_cast<__bf16 *>(dU) + (base) + (i);                             \
+    unsigned short h_[VEC];                                                                  \
+    _Pragma("unroll") for (int j_ = 0; j_ < VEC; ++j_)                                       \
+        h_[j_] = __builtin_bit_cast(unsigned short, (__bf16)(o)[j_]);                        \
+    if constexpr (VEC == 4)                                                                  \
+      *reinterpret_cast<uint2 *>(ob_) =                                                      \
+          make_uint2(h_[0] | ((unsigned)h_[1] << 16), h_[2] | ((unsigned)h_[3] << 16));      \
+    else if constexpr (VEC == 2)                                                             \
+      *reinterpret_cast<unsigned *>(ob_) = h_[0] | ((unsigned)h_[1] << 16);                  \
+    else                                                                                     \
+      *reinterpret_cast<unsigned short *>(ob_) = h_[0];                                      \
+  } while (0)
+
 template <int VEC>
 __global__ __launch_bounds__(256) void k_bn_relu_bwd_apply(
     const float *dy, const float *U, const float *mean, const float *invstd, const float *g,
@@ -345,17 +360,10 @@ __global__ __launch_bounds__(256) void k_bn_relu_bwd_apply(
   const int64_t base = ((int64_t)n * C + c) * L;
   const float dv = dync ? dync[(int64_t)n * C + c] : 0.f;  // (ABI 10: dy constant per row)
   drop = dropout_resolve(drop);
-  const float mu = mean[c], is = invstd[c], a = is * g[c], be = b[c];
+  const BnAff bn = bn_aff(mean, invstd, g, b, c);
   const float mg = (float)(sg[c] * invM), mgu = (float)(sgu[c] * invM);
-  // deferred dx of the next block: dy = ca * (dxhat - cmd - (y - cmu) * cis * cmdn)
-  float ca = 0.f, cmd = 0.f, cmu = 0.f, cis = 0.f, cmdn = 0.f;
-  if (dy_coef) {
-    ca = dy_coef[c];
-    cmd = dy_coef[C + c];
-    cmu = dy_coef[2 * C + c];
-    cis = dy_coef[3 * C + c];
-    cmdn = dy_coef[4 * C + c];
-  }
+  DyCoef dc = {};
+  if (dy_coef) dc.load(dy_coef, C, c);
   double s = 0.0;
   for (int i = threadIdx.x * VEC; i < L; i += 256 * VEC) {
     float u[VEC], d[VEC], o[VEC];
@@ -368,11 +376,7 @@ __global__ __launch_bounds__(256) void k_bn_relu_bwd_apply(
     }
     if (dy_coef) {
 #pragma unroll
-      for (int j = 0; j < VEC; ++j) {
-        const float t = (u[j] - mu) * a + be;
-        const float yv = t > 0.f ? t : 0.f;  // this block's output, as k_bn_relu_fwd wrote it
-        d[j] = ca * (d[j] - cmd - (yv - cmu) * cis * cmdn);
-      }
+      for (int j = 0; j < VEC; ++j) d[j] = dc.dy(d[j], bn_relu(bn.pre(u[j])));
     }
     if (drop.thresh) {
 #pragma unroll
@@ -381,23 +385,11 @@ __global__ __launch_bounds__(256) void k_bn_relu_bwd_apply(
     }
 #pragma unroll
     for (int j = 0; j < VEC; ++j) {
-      const float uh = (u[j] - mu) * is;
-      const float gg = (u[j] - mu) * a + be > 0.f ? d[j] : 0.f;
-      o[j] = a * (gg - mg - uh * mgu);
+      o[j] = bn2_bwd(bn, u[j], d[j], mg, mgu);
       s += o[j];
     }
-    if (du_bf16) {  // dU stored in bf16 (its readers round it to bf16 anyway)
-      __bf16 *ob = reinterpret_cast<__bf16 *>(dU) + base + i;
-      unsigned short h[VEC];
-#pragma unroll
-      for (int j = 0; j < VEC; ++j) h[j] = __builtin_bit_cast(unsigned short, (__bf16)o[j]);
-      if constexpr (VEC == 4)
-        *reinterpret_cast<uint2 *>(ob) = make_uint2(h[0] | ((unsigned)h[1] << 16),
-                                                    h[2] | ((unsigned)h[3] << 16));
-      else if constexpr (VEC == 2)
-        *reinterpret_cast<unsigned *>(ob) = h[0] | ((unsigned)h[1] << 16);
-      else
-        *reinterpret_cast<unsigned short *>(ob) = h[0];
+    if (du_bf16) {
+      STGCN_STORE_DU_BF16(dU, base, i, o);
     } else {
       vst<VEC>(dU + base + i, o);
     }
@@ -438,8 +430,10 @@ __global__ __launch_bounds__(256) void k_bn_relu_bwd_apply_cols(
   const int i = (blockIdx.y * 256 + threadIdx.x) * VEC;
   const int nz = gridDim.z, per = (N + nz - 1) / nz;
   const int n0 = blockIdx.z * per, n1 = min(N, n0 + per);
-  const float mu = mean[c], is = invstd[c], a = is * g[c], be = b[c];
+  const BnAff bn = bn_aff(mean, invstd, g, b, c);
   const float mg = (float)(sg[c] * invM), mgu = (float)(sgu[c] * invM);
+  // (this kernel keeps the five loads as scalars: as a DyCoef captured by the
+  // lambdas below they come out in other registers)
   float ca = 0.f, cmd = 0.f, cmu = 0.f, cis = 0.f, cmdn = 0.f;
   if (dy_coef) {
     ca = dy_coef[c];
@@ -487,11 +481,8 @@ __global__ __launch_bounds__(256) void k_bn_relu_bwd_apply_cols(
       }
       if (dy_coef) {
 #pragma unroll
-        for (int j = 0; j < VEC; ++j) {
-          const float t = (u[j] - mu) * a + be;
-          const float yv = t > 0.f ? t : 0.f;
-          d[j] = ca * (d[j] - cmd - (yv - cmu) * cis * cmdn);
-        }
+        for (int j = 0; j < VEC; ++j)
+          d[j] = ca * (d[j] - cmd - (bn_relu(bn.pre(u[j])) - cmu) * cis * cmdn);
       }
       if (drop.thresh) {
 #pragma unroll
@@ -500,25 +491,13 @@ __global__ __launch_bounds__(256) void k_bn_relu_bwd_apply_cols(
       }
 #pragma unroll
       for (int j = 0; j < VEC; ++j) {
-        const float uh = (u[j] - mu) * is;
-        const float gg = (u[j] - mu) * a + be > 0.f ? d[j] : 0.f;
-        o[j] = a * (gg - mg - uh * mgu);
+        o[j] = bn2_bwd(bn, u[j], d[j], mg, mgu);
         s += o[j];
         col[j] += o[j];
         om = fmaxf(om, fabsf(o[j]));
       }
       if (du_bf16) {
-        __bf16 *ob = reinterpret_cast<__bf16 *>(dU) + base + i;
-        unsigned short h[VEC];
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) h[j] = __builtin_bit_cast(unsigned short, (__bf16)o[j]);
-        if constexpr (VEC == 4)
-          *reinterpret_cast<uint2 *>(ob) = make_uint2(h[0] | ((unsigned)h[1] << 16),
-                                                      h[2] | ((unsigned)h[3] << 16));
-        else if constexpr (VEC == 2)
-          *reinterpret_cast<unsigned *>(ob) = h[0] | ((unsigned)h[1] << 16);
-        else
-          *reinterpret_cast<unsigned short *>(ob) = h[0];
+        STGCN_STORE_DU_BF16(dU, base, i, o);
       } else {
         vst<VEC>(dU + base + i, o);
       }
@@ -567,16 +546,10 @@ __global__ __launch_bounds__(256) void k_bn_relu_bwd_apply_fr(
   const int L = To * V, np = nf * V;
   const int nz = gridDim.z, per = (N + nz - 1) / nz;
   const int n0 = blockIdx.z * per, n1 = min(N, n0 + per);
-  const float mu = mean[c], is = invstd[c], a = is * g[c], be = b[c];
+  const BnAff bn = bn_aff(mean, invstd, g, b, c);
   const float mg = (float)(sg[c] * invM), mgu = (float)(sgu[c] * invM);
-  float ca = 0.f, cmd = 0.f, cmu = 0.f, cis = 0.f, cmdn = 0.f;
-  if (dy_coef) {
-    ca = dy_coef[c];
-    cmd = dy_coef[C + c];
-    cmu = dy_coef[2 * C + c];
-    cis = dy_coef[3 * C + c];
-    cmdn = dy_coef[4 * C + c];
-  }
+  DyCoef dc = {};
+  if (dy_coef) dc.load(dy_coef, C, c);
   // this thread's two output positions of dUA and their columns of A
   const int e0 = tid, e1 = tid + 256;
   const int w0 = e0 % V, w1 = e1 % V, fr0 = e0 / V, fr1 = e1 / V;
@@ -600,14 +573,10 @@ __global__ __launch_bounds__(256) void k_bn_relu_bwd_apply_fr(
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         if (dy_coef) {
-          const float tt = (u[j] - mu) * a + be;
-          const float yv = tt > 0.f ? tt : 0.f;
-          d[j] = ca * (d[j] - cmd - (yv - cmu) * cis * cmdn);
+          d[j] = dc.dy(d[j], bn_relu(bn.pre(u[j])));
         }
         if (drop.thresh) d[j] = dropout_keep(drop, base + pp + j) ? d[j] * drop.scale : 0.f;
-        const float uh = (u[j] - mu) * is;
-        const float gg = (u[j] - mu) * a + be > 0.f ? d[j] : 0.f;
-        o[j] = a * (gg - mg - uh * mgu);
+        o[j] = bn2_bwd(bn, u[j], d[j], mg, mgu);
         s += o[j];
         om = fmaxf(om, fabsf(o[j]));
       }
@@ -770,14 +739,14 @@ __global__ __launch_bounds__(256) void k_bn1_bwd_apply(float *dx, const float *x
   // poorly conditioned reconstruction (or g2 == 0 / non-finite): use U
   const bool from_u = pg2 && pU && !(fabsf(pb) <= 4.f * fabsf(pg));
   const float pmu = from_u ? pmean[c] : 0.f, pis = from_u ? pinvstd[c] : 1.f;
-  const float pa = pis * pg;
+  const BnAff pbn = {pmu, pis, pis * pg, pb};  // the previous block's BN2
   double s = 0.0, q = 0.0;
   for (int i = threadIdx.x * VEC; i < L; i += 256 * VEC) {
     float xv[VEC], d[VEC];
     vld<VEC>(x + base + i, xv);
     vld<VEC>(dx + base + i, d);
 #pragma unroll
-    for (int j = 0; j < VEC; ++j) d[j] = a * (d[j] - md - (xv[j] - mu) * is * mdn);
+    for (int j = 0; j < VEC; ++j) d[j] = a * (d[j] - md - bn_hat(xv[j], mu, is) * mdn);
     if (add) {
       float r[VEC];
       vld<VEC>(add + base + i, r);
@@ -790,9 +759,9 @@ __global__ __launch_bounds__(256) void k_bn1_bwd_apply(float *dx, const float *x
       vld<VEC>(pU + base + i, u);
 #pragma unroll
       for (int j = 0; j < VEC; ++j)
-        if ((u[j] - pmu) * pa + pb > 0.f) {
+        if (pbn.pre(u[j]) > 0.f) {
           s += d[j];
-          q += (double)d[j] * (double)((u[j] - pmu) * pis);
+          q += (double)d[j] * (double)pbn.hat(u[j]);
         }
     } else if (pg2) {
 #pragma unroll

@@ -37,8 +37,11 @@
 
 namespace stgcn {
 
-template <int V, int K>
-struct SpFwdGeo {
+// The geometry both fused forward kernels share: NT threads, ROWS output rows
+// per workgroup (k_sp_fwd_bf16: 256, 64; k_sp_fwd_wide: 512, all rows).
+template <int V, int K, int NT_, int ROWS>
+struct SpFwdGeoBase {
+  static constexpr int NT = NT_;
   static constexpr int FT = kTileCols / V;
   static constexpr int NCOLS = FT * V;
   static constexpr int CK = 16;                    // input channels per chunk
@@ -54,18 +57,23 @@ struct SpFwdGeo {
   static constexpr int X_BYTES = RT * 32 * XP * 2;
   static constexpr int A_BYTES = GC * 32 * XP * 2;  // one plane
   static constexpr int G_BYTES = NCOLS * SLOTS * 16;
-  static constexpr int W_BYTES = K * 2 * 1024;     // packed W' chunk
+  static constexpr int W_BYTES = K * 2 * ROWS * 16;  // packed W' chunk
   static constexpr int NIT = CK * NCOLS;           // x staging items (ch, pos)
-  static constexpr int IPT = (NIT + 255) / 256;
+  static constexpr int IPT = (NIT + NT - 1) / NT;
   // layout: [A h][A m][X][G][W0][W1][BN tables 2 x 3 x 16 floats]
   static constexpr int A_IMG = (2 * A_BYTES + 1023) & ~1023;  // both planes, whole KiB
   static constexpr int OFF_AH = 0, OFF_AM = A_BYTES, OFF_X = A_IMG;
   static constexpr int OFF_G = OFF_X + X_BYTES, OFF_W = OFF_G + G_BYTES;
   static constexpr int OFF_BN = OFF_W + 2 * W_BYTES;
-  static constexpr int LDS = OFF_BN + 2 * 6 * 16 * 4;
+  static constexpr int MAIN = OFF_BN + 2 * 6 * 16 * 4;  // end of the main loop's images
+};
+
+template <int V, int K>
+struct SpFwdGeo : SpFwdGeoBase<V, K, 256, 64> {
+  static constexpr int LDS = SpFwdGeo::MAIN;
   static_assert(LDS <= 160 * 1024, "LDS budget");
   static_assert(LDS >= 2048 + 64 * V * 4, "epilogue scratch fits");
-  static_assert(IPT <= 16, "staging registers");
+  static_assert(SpFwdGeo::IPT <= 16, "staging registers");
 };
 
 struct SpFwdParams {
@@ -80,6 +88,34 @@ struct SpFwdParams {
   int C, T, relu, nchunks;
   ConvGemmParams ep;  // epilogue: out = Z, bias_rv, stats, R, V, M, T_dst, tiles
 };
+
+// the chunk's BN table [6][16] (mean, a, beta of BN1; then of the previous
+// block's BN2) into slot, by the first 16 threads
+template <class G>
+__device__ __forceinline__ void spf_bn_table(const SpFwdParams &P, float *bnt, int chunk,
+                                             int slot, int tid) {
+  if (tid < 16) {
+    const int c = chunk * G::CK + tid;
+    float mu = 0.f, a = 0.f, be = 0.f, pmu = 0.f, pa = 0.f, pbe = 0.f;
+    if (c < P.C) {
+      mu = P.mean[c];
+      a = P.invstd[c] * P.g[c];
+      be = P.b[c];
+      if (P.pmean) {
+        pmu = P.pmean[c];
+        pa = P.pinvstd[c] * P.pg[c];
+        pbe = P.pb[c];
+      }
+    }
+    float *tb = bnt + slot * 96;
+    tb[tid] = mu;
+    tb[16 + tid] = a;
+    tb[32 + tid] = be;
+    tb[48 + tid] = pmu;
+    tb[64 + tid] = pa;
+    tb[80 + tid] = pbe;
+  }
+}
 
 #define SPF_ST16(k)                                                                        \
   "+v"(st[k + 0]), "+v"(st[k + 1]), "+v"(st[k + 2]), "+v"(st[k + 3]), "+v"(st[k + 4]),   \
@@ -148,29 +184,6 @@ __global__ __launch_bounds__(256, 2) void k_sp_fwd_bf16(SpFwdParams P) {
                    : "memory");
   };
   float *bnt = reinterpret_cast<float *>(lds + G::OFF_BN);  // [2][6][16]: mean, a, beta; prev
-  auto bn_table = [&](int chunk, int slot) {
-    if (tid < 16) {
-      const int c = chunk * G::CK + tid;
-      float mu = 0.f, a = 0.f, be = 0.f, pmu = 0.f, pa = 0.f, pbe = 0.f;
-      if (c < P.C) {
-        mu = P.mean[c];
-        a = P.invstd[c] * P.g[c];
-        be = P.b[c];
-        if (P.pmean) {
-          pmu = P.pmean[c];
-          pa = P.pinvstd[c] * P.pg[c];
-          pbe = P.pb[c];
-        }
-      }
-      float *tb = bnt + slot * 96;
-      tb[tid] = mu;
-      tb[16 + tid] = a;
-      tb[32 + tid] = be;
-      tb[48 + tid] = pmu;
-      tb[64 + tid] = pa;
-      tb[80 + tid] = pbe;
-    }
-  };
   auto write_x = [&](int chunk, int slot) {
     __bf16 *xi = reinterpret_cast<__bf16 *>(lds + G::OFF_X);
     const float *tb = bnt + slot * 96;
@@ -222,7 +235,7 @@ __global__ __launch_bounds__(256, 2) void k_sp_fwd_bf16(SpFwdParams P) {
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[j][i] = 0.f;
 
-  bn_table(0, 0);
+  spf_bn_table<G>(P, bnt, 0, 0, tid);
   dma_w(0, 0);
   load_x(0);
   spf_wait_all(st);
@@ -232,7 +245,7 @@ __global__ __launch_bounds__(256, 2) void k_sp_fwd_bf16(SpFwdParams P) {
     __syncthreads();  // A: X(c) and W'(c) are in LDS; every wave is done with G(c-1)
     const bool more = c + 1 < nch;
     if (more) {
-      bn_table(c + 1, (c + 1) & 1);
+      spf_bn_table<G>(P, bnt, c + 1, (c + 1) & 1, tid);
       dma_w(c + 1, (c + 1) & 1);
       load_x(c + 1);
     }
@@ -348,37 +361,13 @@ __global__ __launch_bounds__(256, 2) void k_sp_fwd_bf16(SpFwdParams P) {
 // The x chunk of the next step is loaded under this chunk's MFMAs.
 // ---------------------------------------------------------------------------
 template <int V, int K, int ROWS>
-struct SpWideGeo {
-  static constexpr int NT = 512;
-  static constexpr int FT = kTileCols / V;
-  static constexpr int NCOLS = FT * V;
-  static constexpr int CK = 16;
-  static constexpr int XROWS = CK * FT;
-  static constexpr int RT = (XROWS + 31) / 32;
-  static constexpr int KW = (V + 15) & ~15;
-  static constexpr int KS = KW / 16;
-  static constexpr int XP = KW + 8;
-  static constexpr int NGC = K * V;
-  static constexpr int GC = (NGC + 31) / 32;
-  static constexpr int GT = RT * GC;
-  static constexpr int SLOTS = 2 * K + 1;
+struct SpWideGeo : SpFwdGeoBase<V, K, 512, ROWS> {
   static constexpr int MB = ROWS / 64;            // 32-row blocks per wave
-  static constexpr int X_BYTES = RT * 32 * XP * 2;
-  static constexpr int A_BYTES = GC * 32 * XP * 2;
-  static constexpr int G_BYTES = NCOLS * SLOTS * 16;
-  static constexpr int W_BYTES = K * 2 * ROWS * 16;  // packed W' chunk
-  static constexpr int NIT = CK * NCOLS;
-  static constexpr int IPT = (NIT + NT - 1) / NT;
-  static constexpr int A_IMG = (2 * A_BYTES + 1023) & ~1023;  // both planes, whole KiB
-  static constexpr int OFF_AH = 0, OFF_AM = A_BYTES, OFF_X = A_IMG;
-  static constexpr int OFF_G = OFF_X + X_BYTES, OFF_W = OFF_G + G_BYTES;
-  static constexpr int OFF_BN = OFF_W + 2 * W_BYTES;
-  static constexpr int MAIN = OFF_BN + 2 * 6 * 16 * 4;
   static constexpr int EROWS = ROWS < 128 ? ROWS : 128;  // LDS-image epilogue rows
   static constexpr int EPI = ROWS == 256 ? 0 : (EROWS * kEpiPitch + EROWS * V) * 4;
-  static constexpr int LDS = MAIN > EPI ? MAIN : EPI;
+  static constexpr int LDS = SpWideGeo::MAIN > EPI ? SpWideGeo::MAIN : EPI;
   static_assert(LDS <= 160 * 1024, "LDS budget");
-  static_assert(IPT == 8, "staging register count");
+  static_assert(SpWideGeo::IPT == 8, "staging register count");
   static_assert(ROWS == 64 || ROWS == 128 || ROWS == 256, "row tiles");
 };
 
@@ -440,29 +429,6 @@ __global__ __launch_bounds__(512, 1) void k_sp_fwd_wide(SpFwdParams P) {
                    "+v"(st[6]), "+v"(st[7])::"memory");
   };
   float *bnt = reinterpret_cast<float *>(lds + G::OFF_BN);  // [2][6][16]: mean, a, beta; prev
-  auto bn_table = [&](int chunk, int slot) {
-    if (tid < 16) {
-      const int c = chunk * G::CK + tid;
-      float mu = 0.f, a = 0.f, be = 0.f, pmu = 0.f, pa = 0.f, pbe = 0.f;
-      if (c < P.C) {
-        mu = P.mean[c];
-        a = P.invstd[c] * P.g[c];
-        be = P.b[c];
-        if (P.pmean) {
-          pmu = P.pmean[c];
-          pa = P.pinvstd[c] * P.pg[c];
-          pbe = P.pb[c];
-        }
-      }
-      float *tb = bnt + slot * 96;
-      tb[tid] = mu;
-      tb[16 + tid] = a;
-      tb[32 + tid] = be;
-      tb[48 + tid] = pmu;
-      tb[64 + tid] = pa;
-      tb[80 + tid] = pbe;
-    }
-  };
   auto write_x = [&](int chunk, int slot) {
     __bf16 *xi = reinterpret_cast<__bf16 *>(lds + G::OFF_X);
     const float *tb = bnt + slot * 96;
@@ -518,7 +484,7 @@ __global__ __launch_bounds__(512, 1) void k_sp_fwd_wide(SpFwdParams P) {
 #pragma unroll
       for (int i = 0; i < 16; ++i) acc[rb][j][i] = 0.f;
 
-  bn_table(0, 0);
+  spf_bn_table<G>(P, bnt, 0, 0, tid);
   dma_w(0, 0);
   load_x(0);
   wait_x();
@@ -528,7 +494,7 @@ __global__ __launch_bounds__(512, 1) void k_sp_fwd_wide(SpFwdParams P) {
     __syncthreads();  // A: X(c) and W'(c) are in LDS; every wave is done with G(c-1)
     const bool more = c + 1 < nch;
     if (more) {
-      bn_table(c + 1, (c + 1) & 1);
+      spf_bn_table<G>(P, bnt, c + 1, (c + 1) & 1, tid);
       dma_w(c + 1, (c + 1) & 1);
       load_x(c + 1);
     }

@@ -759,18 +759,18 @@ __global__ __launch_bounds__(512, 1) void k_sp50_dx(Sp50Params P) {
       float xv = xr[i];
       bool pm = false;
       float uh = 0.f;
-      if (pv) {  // x = ReLU((U - pmu) pa + pb) as the previous block's output pass formed it
-        const float t = (xv - pmu) * pa + pb;
-        uh = (xv - pmu) * pis;
+      if (pv) {
+        const float t = bn_pre(xv, pmu, pa, pb);
+        uh = bn_hat(xv, pmu, pis);
         pm = t > 0.f;
         xv = pm ? t : 0.f;
       }
-      const float bn = (xv - mu) * ga + be;
+      const float bn = bn_pre(xv, mu, ga, be);
       float d = live ? dxa[i] : 0.f;
       if (P.relu && bn <= 0.f) d = 0.f;  // ReLU'(BN1(x)) of the residual block
       dv[i] = d;
       s += d;
-      sn = fmaf(d, (xv - mu) * is, sn);
+      sn = fmaf(d, bn_hat(xv, mu, is), sn);
       if (pm) {
         s1 += d;
         s2 = fmaf(d, uh, s2);
@@ -937,11 +937,8 @@ __global__ __launch_bounds__(512, 1) void k_sp50_dA(Sp50Params P) {
         const int pos = part + 16 * q;
         if (pos < G::NPOS) {
           float xv = xr[q];
-          if (pv) {
-            const float t = (xv - pmu) * pa + pb;
-            xv = t > 0.f ? t : 0.f;
-          }
-          const float bn = (xv - mu) * ga + be;
+          if (pv) xv = bn_relu(bn_pre(xv, pmu, pa, pb));
+          const float bn = bn_pre(xv, mu, ga, be);
           const float fx = pos < live ? (P.relu ? fmaxf(bn, 0.f) : bn) : 0.f;
           xbi[pos * (G::XBP / 2)] = (__bf16)fx;
         }

@@ -340,8 +340,7 @@ __device__ __forceinline__ void spb_epilogue(const ConvGemmParams &p, floatx16 (
         if (ok) {
           const float4 q0 = *reinterpret_cast<const float4 *>(rt + rr * 8);
           const float4 q1 = *reinterpret_cast<const float4 *>(rt + rr * 8 + 4);
-          const float mu = q0.x, is = q0.y, a = q0.z, be = q0.w;
-          const float pmu = q1.x, pis = q1.y, pa = q1.z, pb = q1.w;
+          const BnAff bn1 = {q0.x, q0.y, q0.z, q0.w}, pbn = {q1.x, q1.y, q1.z, q1.w};
           const int c = r0 + h * 64 + rr;
           const float *hr = Himg + rr * P + f * V;
           float hv[V];
@@ -373,15 +372,15 @@ __device__ __forceinline__ void spb_epilogue(const ConvGemmParams &p, floatx16 (
           for (int e = 0; e < 6; ++e) {
             float xx = xs[e], uh = 0.f;
             bool pm = false;
-            if (pv) {  // the previous block's output x = ReLU(BN2(U)) as its output pass formed it
-              const float t = (xx - pmu) * pa + pb;
-              uh = (xx - pmu) * pis;
+            if (pv) {
+              const float t = pbn.pre(xx);
+              uh = pbn.hat(xx);
               pm = t > 0.f;
               xx = pm ? t : 0.f;
             }
-            const float bn = (xx - mu) * a + be;
+            const float bn = bn1.pre(xx);
             if (need_s0) s0 += d[e];
-            s1 = fmaf(d[e], (xx - mu) * is, s1);
+            s1 = fmaf(d[e], bn1.hat(xx), s1);
             if (pm) {
               s2 += d[e];
               s3 = fmaf(d[e], uh, s3);

@@ -56,13 +56,10 @@ __global__ __launch_bounds__(256) void k_head_pool_u(const float *U, const float
   const int lane = threadIdx.x & 63;
   if (row >= rows) return;
   const int c = (int)(row % C);
-  const float mu = mean[c], a = invstd[c] * g[c], be = b[c];
+  const stgcn::BnAff bn = stgcn::bn_aff(mean, invstd, g, b, c);
   const float *src = U + row * L;
   float s = 0.f;
-  for (int l = lane; l < L; l += 64) {
-    const float t = (src[l] - mu) * a + be;
-    s += t > 0.f ? t : 0.f;
-  }
+  for (int l = lane; l < L; l += 64) s += stgcn::bn_relu(bn.pre(src[l]));
   s = wave_sumf(s);
   if (lane == 0) pooled[row] = s / (float)L;
 }
