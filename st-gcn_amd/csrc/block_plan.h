@@ -108,7 +108,8 @@ inline bool projection(const stgcn_desc_t *d) {
 // "supported?" or a size question); the ConvGemmParams come back tiled. A call
 // site adds only what is its own: the epilogue extras (bias_r, stat_*, res,
 // relu_out, drop), the operands' storage format (in_bf16), the f16x2 bound
-// pointers, the spb / bna operand block, dA_part and wpk_ready.
+// pointers, the spb / bna operand block, dA_part and wpk_ready. The spatial
+// launches' descriptors follow the same rule (spatial_fwd / spatial_bwd below).
 
 inline ConvGemmParams conv_base(const stgcn_desc_t *d, float *wpk) {
   ConvGemmParams p{};
@@ -395,11 +396,52 @@ inline WgradParams make_wgrad_taps(const stgcn_desc_t *d, const float *dU, const
 // its statistics [mean | invstd] over C channels, gamma2 and beta2
 inline PrevBn prev_bn(const float *prev_stats, int C, const float *g2, const float *b2) {
   PrevBn pv;
-  pv.mean = prev_stats;
-  pv.invstd = prev_stats + C;
-  pv.g = g2;
-  pv.b = b2;
+  pv.bn = bn_ref(prev_stats, C, g2, b2);
   return pv;
+}
+
+// The spatial launches (internal.h SpatialFwd / SpatialBwd): the shape, BN1 and
+// the residual block's ReLU on BN1(x) from the descriptor. A call site adds what
+// is its own: the outputs of the kernel it launches (G, amax | W, biasZ, wpk, Z,
+// Gk, the Z sums), prev, the dA partial slots, only.
+inline SpatialFwd spatial_fwd(const stgcn_desc_t *d, const float *x, const BnRef &bn1,
+                              const float *A) {
+  SpatialFwd f;
+  f.x = x;
+  f.bn = bn1;
+  f.A = A;
+  f.N = d->N;
+  f.C = d->C_in;
+  f.R = d->C_out;
+  f.T = d->T;
+  f.V = d->V;
+  f.K = d->K;
+  f.relu = residual(d) ? 1 : 0;
+  return f;
+}
+// in: dZ (launch_sp_bwd_fused, with W and wpk) or H = W'^T dZ (launch_spatial_dx)
+inline SpatialBwd spatial_bwd(const stgcn_desc_t *d, const float *in, const float *x,
+                              const BnRef &bn1, const float *A, float *dx, float *dA, double *sd,
+                              double *sdn) {
+  SpatialBwd b;
+  b.in = in;
+  b.x = x;
+  b.bn = bn1;
+  b.A = A;
+  b.dx = dx;
+  b.dA = dA;
+  b.sd = sd;
+  b.sdn = sdn;
+  b.N = d->N;
+  b.C = d->C_in;
+  b.R = d->C_out;
+  b.T = d->T;
+  b.V = d->V;
+  b.K = d->K;
+  b.write_dx = d->need_dx;
+  b.relu = residual(d) ? 1 : 0;
+  b.bf16ops = bf16(d) ? 1 : 0;
+  return b;
 }
 
 // ---- Path predicates that ask a built launch ----

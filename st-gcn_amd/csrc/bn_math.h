@@ -10,6 +10,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "internal.h"  // BnRef
+
 namespace stgcn {
 
 // BN(x) with a = invstd * g, and xhat, on per-channel values the kernel holds
@@ -29,6 +31,9 @@ __device__ __forceinline__ BnAff bn_aff(const float *mean, const float *invstd, 
   BnAff r = {mean[c], invstd[c]};
   r.a = r.is * g[c], r.be = b[c];
   return r;
+}
+__device__ __forceinline__ BnAff bn_aff(const BnRef &bn, int c) {
+  return bn_aff(bn.mean, bn.invstd, bn.g, bn.b, c);
 }
 
 // The element of y = ReLU(BN2(u)): y, the mask m = y > 0 and uhat, as

@@ -235,7 +235,8 @@ struct FwdCtx {
   PrepLayout P;
   bool stat_parts;  // the folded forward on k_conv_x3: BN2 statistics as per-tile partials
   bool no_memset;
-  float *mean1, *invstd1, *mean2, *invstd2;
+  float *st1, *st2;  // [mean | invstd] of BN1 / BN2 in a->stats (the finalize kernels' output)
+  BnRef bn1, bn2;    // ... with gamma and beta, as the kernels read them
   const unsigned *xmax = nullptr;  // (bna: max |x|, the fp16 operand bound's input)
   const uint64_t *seed_dev = nullptr;  // the dropout's step token (stgcn_block_fwd_dseed)
   const float *Gfold = nullptr;    // the folded block's G (spatial stage -> temporal stage)
@@ -309,7 +310,7 @@ int fwd_bn1_stats(FwdCtx &c, void *workspace) {
     HIP_TRY(launch_absmax(a->x, (int64_t)N * C * T * V, L.amax, s));
   }
   HIP_TRY(launch_bn_finalize(xs1, xq1, C, (int64_t)N * T * V, d->eps, d->momentum, d->training,
-                             a->rm1, a->rv1, c.mean1, c.invstd1, s,
+                             a->rm1, a->rv1, c.st1, c.st1 + C, s,
                              c.no_memset ? L.amax : nullptr, c.no_memset ? 2 * kAmaxWords : 0));
   return STGCN_OK;
 }
@@ -330,25 +331,29 @@ int fwd_spatial(FwdCtx &c) {
     Wz = L.Wpk;
   }
   // (x = ReLU(BN2_prev(prev_U)) formed on staging / on load)
-  const PrevBn pv = xu ? prev_bn(a->prev_stats, C, a->prev_g2, a->prev_b2) : PrevBn();
+  SpatialFwd f = spatial_fwd(d, xu ? a->prev_U : a->x, c.bn1, a->A);
+  if (xu) f.prev = prev_bn(a->prev_stats, C, a->prev_g2, a->prev_b2);
   if (fused_sp(d)) {
     // bf16 path: BN1 + joint contraction + W' GEMM in one kernel; G kept in bf16
     // for the backward when the caller asks (stgcn_keep_g_bytes)
-    HIP_TRY(launch_sp_fwd_bf16(xu ? a->prev_U : a->x, c.mean1, c.invstd1, a->g1, a->b1, a->A,
-                               a->W, L.biasZ, L.wpk, a->Z, z_bf16(d) ? 1 : 0,
-                               reinterpret_cast<__bf16 *>(a->G),
-                               (res && d->training) ? L.s2 : nullptr,
-                               (res && d->training) ? L.q2 : nullptr, N, C, R, T, V, K, res, s,
-                               xu ? &pv : nullptr));
+    f.W = a->W;
+    f.biasZ = L.biasZ;
+    f.wpk = L.wpk;
+    f.Z = a->Z;
+    f.z_bf16 = z_bf16(d) ? 1 : 0;
+    f.Gk = reinterpret_cast<__bf16 *>(a->G);
+    if (res && d->training) {  // BN2 of the residual block normalizes Z (:76)
+      f.ssum = L.s2;
+      f.ssq = L.q2;
+    }
+    HIP_TRY(launch_sp_fwd_bf16(f, s));
   } else if (!c.bna) {
-    float *G = a->G ? a->G : L.G;  // kept for the backward when the caller asks
-    HIP_TRY(launch_gather_fwd(xu ? a->prev_U : a->x, c.mean1, c.invstd1, a->g1, a->b1, a->A, G,
-                              N, C, T, V, K, res, s,
-                              f16x2(d) ? L.amax : nullptr,  // (f16x2: max |G|)
-                              xu ? &pv : nullptr));
-    c.Gfold = G;
+    f.G = a->G ? a->G : L.G;  // kept for the backward when the caller asks
+    f.amax = f16x2(d) ? L.amax : nullptr;  // (f16x2: max |G|)
+    HIP_TRY(launch_gather_fwd(f, s));
+    c.Gfold = f.G;
     if (!c.fold) {
-      ConvGemmParams p = spatial_gemm(d, G, Wz, a->Z, L.biasZ, L.wpk);
+      ConvGemmParams p = spatial_gemm(d, f.G, Wz, a->Z, L.biasZ, L.wpk);
       if (res && d->training) {  // BN2 of the residual block normalizes Z (:76)
         p.stat_sum = L.s2;
         p.stat_sq = L.q2;
@@ -373,9 +378,8 @@ int residual_fwd_tail(FwdCtx &c) {
   hipStream_t s = c.s;
   const int N = d->N, R = d->C_out, T = d->T, To = d->T_out, V = d->V;
   HIP_TRY(launch_bn_finalize(L.s2, L.q2, R, (int64_t)N * T * V, d->eps, d->momentum,
-                             d->training, a->rm2, a->rv2, c.mean2, c.invstd2, s));
-  HIP_TRY(launch_bn_relu_fwd(a->Z, c.mean2, c.invstd2, a->g2, a->b2, a->Za, N, R, T * V, nullptr,
-                             nullptr, Dropout(), s));
+                             d->training, a->rm2, a->rv2, c.st2, c.st2 + R, s));
+  HIP_TRY(launch_bn_relu_fwd(a->Z, c.bn2, a->Za, N, R, T * V, nullptr, nullptr, Dropout(), s));
   const float *resid = a->x;
   if (projection(d)) {  // apply_residual: Conv2d(C_in, C_out, 1, stride (s,1)) (:27)
     HIP_TRY(launch_conv_gemm(proj_fwd(d, a->x, a->Wr, L.Rp, a->br, L.wpk), s));
@@ -440,10 +444,7 @@ int fwd_temporal(FwdCtx &c) {
       p.bna = 1;
       p.amax_in = c.xmax;
       p.sA = a->A;
-      p.mean1 = c.mean1;
-      p.invstd1 = c.invstd1;
-      p.g1 = a->g1;
-      p.b1 = a->b1;
+      p.bn1 = c.bn1;
       // (the kept "G" buffer holds only max |x|, for the backward's weight gradient)
       p.amax_keep = a->G ? reinterpret_cast<unsigned *>(a->G) : nullptr;
     }
@@ -480,11 +481,11 @@ int fwd_bn2_out(FwdCtx &c) {
   double *ys = (d->training && a->y_stats) ? a->y_stats : nullptr;
   if (c.stat_parts)  // (zeroes y_stats on the way)
     HIP_TRY(launch_bn_finalize_parts(L.s2part, fold_stat_tiles(d), R, (int64_t)N * To * V, d->eps,
-                                     d->momentum, d->training, a->rm2, a->rv2, c.mean2, c.invstd2,
-                                     s, ys, kAmaxWords));
+                                     d->momentum, d->training, a->rm2, a->rv2, c.st2, c.st2 + R, s,
+                                     ys, kAmaxWords));
   else
     HIP_TRY(launch_bn_finalize(L.s2, L.q2, R, (int64_t)N * To * V, d->eps, d->momentum,
-                               d->training, a->rm2, a->rv2, c.mean2, c.invstd2, s));
+                               d->training, a->rm2, a->rv2, c.st2, c.st2 + R, s));
   const Dropout ydrop = make_dropout(d, a->dropout_p, a->seed, c.seed_dev);
   // (ABI 5: y_stats holds 5 * C_out sums; the last three -- over the ReLU mask --
   // feed the next block's deferred-dx chain, meaningless under dropout; ABI 7:
@@ -493,8 +494,7 @@ int fwd_bn2_out(FwdCtx &c) {
   // nothing -- the consumer forms ReLU(BN2(U)) itself)
   if (!a->y && !ys) return STGCN_OK;
   if (ys && !c.stat_parts) HIP_TRY(hipMemsetAsync(ys, 0, y_stats_bytes(R), s));
-  HIP_TRY(launch_bn_relu_fwd(a->U, c.mean2, c.invstd2, a->g2, a->b2, a->y, N, R, To * V, ys,
-                             ys ? ys + R : nullptr, ydrop, s,
+  HIP_TRY(launch_bn_relu_fwd(a->U, c.bn2, a->y, N, R, To * V, ys, ys ? ys + R : nullptr, ydrop, s,
                              (ys && !ydrop.thresh) ? ys + 2 * R : nullptr,
                              ys ? reinterpret_cast<unsigned *>(ys + 5 * R) : nullptr));
   return STGCN_OK;
@@ -525,10 +525,10 @@ extern "C" int stgcn_block_fwd_dseed(const stgcn_desc_t *d, const stgcn_fwd_args
   c.P = c.pre ? prep_layout(d, a->prep) : PrepLayout{};
   c.stat_parts = fold_stat_parts(d) && c.L.s2part;
   c.no_memset = c.stat_parts && a->x_stats;
-  c.mean1 = a->stats;
-  c.invstd1 = a->stats + d->C_in;
-  c.mean2 = a->stats + 2 * d->C_in;
-  c.invstd2 = a->stats + 2 * d->C_in + d->C_out;
+  c.st1 = a->stats;
+  c.st2 = a->stats + 2 * d->C_in;
+  c.bn1 = bn_ref(c.st1, d->C_in, a->g1, a->b1);
+  c.bn2 = bn_ref(c.st2, d->C_out, a->g2, a->b2);
   STAGE(fwd_bn1_stats(c, workspace));
   STAGE(fwd_spatial(c));
   if (c.res) return residual_fwd_tail(c);
@@ -547,7 +547,7 @@ struct BwdCtx {
   bool res;
   bool defer;  // deferred dx (ABI 5; bwd_spatial_dgrad)
   Dropout drop;
-  const float *mean1, *invstd1, *mean2, *invstd2;
+  BnRef bn1, bn2;
   // (Tq's fp64 re-layout goes straight into launch_fold_sdz's scratch slot in
   // this call's workspace -- never into the prep buffer, which holds only the
   // step's weight-only operands and may be shared by concurrent backwards)
@@ -612,6 +612,24 @@ int bwd_check_args(const stgcn_desc_t *d, const stgcn_bwd_args_t *a, void *works
   return STGCN_OK;
 }
 
+// A ReLU + BN2 backward over U (N, C_out, L) with the workspace's sums: what the
+// block's own (bwd_relu_bn2) and the residual block's over Z share
+Bn2Bwd bn2_bwd(const BwdCtx &c, const float *dy, const float *U, float *dU, int L) {
+  Bn2Bwd q;
+  q.dy = dy;
+  q.U = U;
+  q.bn = c.bn2;
+  q.sg = c.L.sg;
+  q.sgu = c.L.sgu;
+  q.dU = dU;
+  q.sdu = c.L.sdu;
+  q.N = c.d->N;
+  q.C = c.d->C_out;
+  q.L = L;
+  q.training = c.d->training;
+  return q;
+}
+
 // Non-residual block: ReLU + BN2 backward -> dU, dgamma2, dbeta2, d(temporal
 // bias); the reduction comes from the next block when it was chained (dy_sums).
 // Residual block: final ReLU backward -> dU (= d(conv out) = d(residual));
@@ -630,39 +648,41 @@ int bwd_relu_bn2(BwdCtx &c) {
                                 nullptr, s));
     return STGCN_OK;
   }
-  const double *sg = L.sg, *sgu = L.sgu;
+  Bn2Bwd q = bn2_bwd(c, a->dy, a->U, L.dU, To * V);
+  q.dy_nc = a->dy_nc;
+  q.drop = drop;
+  q.du_bf16 = du_bf16(d) ? 1 : 0;
+  q.dy_coef = a->dy_coef;
   if (a->dy_sums) {
-    sg = a->dy_sums;
-    sgu = a->dy_sums + R;
+    q.sg = a->dy_sums;
+    q.sgu = a->dy_sums + R;
   } else {
-    HIP_TRY(launch_bn_relu_bwd_reduce(a->dy, a->U, c.mean2, c.invstd2, a->g2, a->b2, N, R, To * V,
-                                      L.sg, L.sgu, drop, s, a->dy_nc));
+    HIP_TRY(launch_bn_relu_bwd_reduce(q, L.sg, L.sgu, s));
   }
   // (with the clip-chunk sums of dU: sum_{n,t} dZ follows from them per tap,
   // no pass over dZ)
   if (cols_sums(d)) {
-    if (fold_bna(d))  // + dU A (the weight gradient's P) in dZ's buffer
-      HIP_TRY(launch_bn_relu_bwd_apply_fr(a->dy, a->U, c.mean2, c.invstd2, a->g2, a->b2, sg, sgu,
-                                          L.dU, L.dZ, L.sdu, N, R, To, V, d->training, drop,
-                                          a->dy_coef, L.fcs, L.amax, L.amax + 2 * kAmaxWords,
-                                          a->A, s));
-    else
-      HIP_TRY(launch_bn_relu_bwd_apply_cols(a->dy, a->U, c.mean2, c.invstd2, a->g2, a->b2, sg,
-                                            sgu, L.dU, L.sdu, N, R, To * V, d->training, drop, s,
-                                            du_bf16(d) ? 1 : 0, a->dy_coef, L.fcs,
-                                            f16x2_tw(d) ? L.amax : nullptr,  // (f16x2: max |dU|)
-                                            a->dy_nc));
+    q.cs = L.fcs;
+    if (fold_bna(d)) {  // + dU A (the weight gradient's P) in dZ's buffer
+      q.dUA = L.dZ;
+      q.amax = L.amax;
+      q.amaxa = L.amax + 2 * kAmaxWords;
+      q.A = a->A;
+      q.V = V;
+      HIP_TRY(launch_bn_relu_bwd_apply_fr(q, s));
+    } else {
+      q.amax = f16x2_tw(d) ? L.amax : nullptr;  // (f16x2: max |dU|)
+      HIP_TRY(launch_bn_relu_bwd_apply_cols(q, s));
+    }
     // (fork: the small kernels from here to launch_chain_coef need the apply
     // pass's sums, never the GEMMs' tensors)
     if (c.overlap) HIP_TRY(c.fk.begin(s));
     HIP_TRY(launch_fold_tq(L.fcs, apply_cols_chunks(N), R, T, To, V, d->stride, L.ftq, c.tqT,
                            c.side()));
   } else {
-    HIP_TRY(launch_bn_relu_bwd_apply(a->dy, a->U, c.mean2, c.invstd2, a->g2, a->b2, sg, sgu, L.dU,
-                                     L.sdu, N, R, To * V, d->training, drop, s,
-                                     du_bf16(d) ? 1 : 0, a->dy_coef, a->dy_nc));
+    HIP_TRY(launch_bn_relu_bwd_apply(q, s));
   }
-  HIP_TRY(launch_bn_grads_out(sg, sgu, L.sdu, R, a->dg2, a->db2, a->dbWt, c.side()));
+  HIP_TRY(launch_bn_grads_out(q.sg, q.sgu, L.sdu, R, a->dg2, a->db2, a->dbWt, c.side()));
   return STGCN_OK;
 }
 
@@ -734,10 +754,7 @@ int bwd_fold_temporal(BwdCtx &c) {
         p.out = d->need_dx ? a->dx : nullptr;
         p.sx = c.xin;
         p.sA = a->A;
-        p.mean1 = c.mean1;
-        p.invstd1 = c.invstd1;
-        p.g1 = a->g1;
-        p.b1 = a->b1;
+        p.bn1 = c.bn1;
         if (c.defer) p.prev = c.pvb;
         p.sd = L.sd;
         p.sd_given = 1;
@@ -769,17 +786,16 @@ int bwd_fold_temporal(BwdCtx &c) {
     w.f16x2 = 1;
     w.amax_p = L.amax + 2 * kAmaxWords;
     w.amax_q = xmax;
-    w.q_mean = c.mean1;
-    w.q_invstd = c.invstd1;
-    w.q_g = a->g1;
-    w.q_b = a->b1;
+    w.q_bn = c.bn1;
   } else {
     const float *G = a->G;  // kept fp32 G (f16x2: its max |G| follows it), else recomputed
     const unsigned *amax_g = G ? reinterpret_cast<const unsigned *>(G + (size_t)N * C * T * V)
                                : L.amax + 2 * kAmaxWords;
     if (!G) {
-      HIP_TRY(launch_gather_fwd(a->x, c.mean1, c.invstd1, a->g1, a->b1, a->A, L.G, N, C, T, V, K,
-                                c.res, s, f16x2(d) ? L.amax + 2 * kAmaxWords : nullptr));
+      SpatialFwd f = spatial_fwd(d, a->x, c.bn1, a->A);
+      f.G = L.G;
+      f.amax = f16x2(d) ? L.amax + 2 * kAmaxWords : nullptr;
+      HIP_TRY(launch_gather_fwd(f, s));
       G = L.G;
     }
     w = make_wgrad_taps(d, L.dU, G, L.slab, C);
@@ -833,10 +849,9 @@ int bwd_unfold_temporal(BwdCtx &c) {
   }
   if (c.res) {
     // BN2 + ReLU backward over Z (residual block, st_graphconv.py:76-77): dZ in place
-    HIP_TRY(launch_bn_relu_bwd_reduce(L.dZ, a->Z, c.mean2, c.invstd2, a->g2, a->b2, N, R, T * V,
-                                      L.sg, L.sgu, Dropout(), s));
-    HIP_TRY(launch_bn_relu_bwd_apply(L.dZ, a->Z, c.mean2, c.invstd2, a->g2, a->b2, L.sg, L.sgu,
-                                     L.dZ, L.sdu, N, R, T * V, d->training, Dropout(), s));
+    const Bn2Bwd q = bn2_bwd(c, L.dZ, a->Z, L.dZ, T * V);
+    HIP_TRY(launch_bn_relu_bwd_reduce(q, L.sg, L.sgu, s));
+    HIP_TRY(launch_bn_relu_bwd_apply(q, s));
     HIP_TRY(launch_bn_grads_out(L.sg, L.sgu, nullptr, R, a->dg2, a->db2, nullptr, s));
   }
   return STGCN_OK;
@@ -862,8 +877,9 @@ int bwd_spatial_wgrad(BwdCtx &c) {
   } else {
     const float *G = fused_sp(d) ? nullptr : a->G;  // kept fp32 G, else recomputed
     if (!G) {
-      HIP_TRY(launch_gather_fwd(a->x, c.mean1, c.invstd1, a->g1, a->b1, a->A, L.G, N, C, T, V, K,
-                                c.res, s));
+      SpatialFwd f = spatial_fwd(d, a->x, c.bn1, a->A);
+      f.G = L.G;
+      HIP_TRY(launch_gather_fwd(f, s));
       G = L.G;
     }
     w = wgrad_spatial(d, L.dZ, G, L.slab);
@@ -887,7 +903,7 @@ int bwd_spatial_dgrad(BwdCtx &c) {
   const stgcn_bwd_args_t *a = c.a;
   const BwdLayout &L = c.L;
   hipStream_t s = c.s;
-  const int N = d->N, C = d->C_in, R = d->C_out, T = d->T, V = d->V, K = d->K;
+  const int C = d->C_in, R = d->C_out, V = d->V, K = d->K;
   // (done in the folded block's data gradient: kernels_x3.hip spb_epilogue)
   if (fold_spb(d)) return STGCN_OK;
   // sum_{n,t} dZ: from the temporal weight and the per-tap dU sums on the
@@ -896,11 +912,15 @@ int bwd_spatial_dgrad(BwdCtx &c) {
   if (cols_sums(d))
     HIP_TRY(launch_fold_sdz(L.f64scr, a->Wt, nullptr, L.ftq, R, C, V, L.SdZ, nullptr, s));
   HIP_TRY(launch_spatial_small(L.SdZ, a->A, a->bW, K, R, V, a->dbW, a->dA, s));
+  // (fused: from dZ; else from H, which the H GEMM or the folded data gradient wrote)
+  SpatialBwd b = spatial_bwd(d, fused_spb(d) ? L.dZ : L.H, c.xin, c.bn1, a->A, a->dx, a->dA, L.sd,
+                             L.sdn);
+  if (c.defer) b.prev = c.pvb;
   if (fused_spb(d)) {
     // H = W'^T dZ, dx = sum_k H_k A_k, dA, BN1 sums in one kernel (H stays on chip)
-    HIP_TRY(launch_sp_bwd_fused(L.dZ, c.xin, c.mean1, c.invstd1, a->g1, a->b1, a->A, a->W, L.wpk,
-                                a->dx, a->dA, L.sd, L.sdn, N, C, R, T, V, K, d->need_dx, c.res,
-                                s, c.defer ? &c.pvb : nullptr));
+    b.W = a->W;
+    b.wpk = L.wpk;
+    HIP_TRY(launch_sp_bwd_fused(b, s));
     return STGCN_OK;
   }
   // The H GEMM and the joint kernel run over the whole batch at once (clip
@@ -916,9 +936,10 @@ int bwd_spatial_dgrad(BwdCtx &c) {
   }
   // (deterministic dA: the joint kernel's workgroup partials, if it takes them)
   int64_t sparts = 0;
-  HIP_TRY(launch_spatial_dx(L.H, c.xin, c.mean1, c.invstd1, a->g1, a->b1, a->A, a->dx, a->dA,
-                            L.sd, L.sdn, N, C, T, V, K, d->need_dx, c.res, bf16(d) ? 1 : 0, s,
-                            c.defer ? &c.pvb : nullptr, L.dApart, L.dA_cap, &sparts));
+  b.dA_part = L.dApart;
+  b.part_cap = L.dA_cap;
+  b.nparts = &sparts;
+  HIP_TRY(launch_spatial_dx(b, s));
   HIP_TRY(launch_dA_reduce(L.dApart, sparts, K * V * V, L.dAlvl, a->dA, s));
   return STGCN_OK;
 }
@@ -932,9 +953,8 @@ int bwd_bn1_tail(BwdCtx &c) {
   hipStream_t s = c.s;
   const int N = d->N, C = d->C_in, R = d->C_out, T = d->T, V = d->V;
   if (c.defer) {  // (forked: after launch_dA_reduce on the side stream, beside launch_fold_grads)
-    HIP_TRY(launch_chain_coef(L.sd, L.sdn, c.mean1, c.invstd1, a->g1, L.s1, L.s2, a->x_stats, C,
-                              (int64_t)N * T * V, a->dg1, a->db1, a->dx_coef, a->prev_sums,
-                              c.side()));
+    HIP_TRY(launch_chain_coef(L.sd, L.sdn, c.bn1, L.s1, L.s2, a->x_stats, C, (int64_t)N * T * V,
+                              a->dg1, a->db1, a->dx_coef, a->prev_sums, c.side()));
     return STGCN_OK;
   }
   HIP_TRY(launch_bn_grads_out(L.sd, L.sdn, nullptr, C, a->dg1, a->db1, nullptr, s));
@@ -955,12 +975,12 @@ int bwd_bn1_tail(BwdCtx &c) {
     const bool chain = d->training && a->prev_g2 && a->prev_b2 && a->prev_sums;
     const bool chain_u = chain && a->prev_U && a->prev_stats;
     if (chain) HIP_TRY(hipMemsetAsync(a->prev_sums, 0, sizeof(double) * 2 * C, s));
-    HIP_TRY(launch_bn1_bwd_apply(a->dx, a->x, c.mean1, c.invstd1, a->g1, L.sd, L.sdn, add, N, C,
-                                 T * V, (int64_t)N * T * V, d->training,
-                                 chain ? a->prev_g2 : nullptr, chain ? a->prev_b2 : nullptr,
-                                 chain ? a->prev_sums : nullptr, chain_u ? a->prev_U : nullptr,
-                                 chain_u ? a->prev_stats : nullptr,
-                                 chain_u ? a->prev_stats + C : nullptr, s));
+    BnRef pbn2;  // the previous block's BN2: gamma / beta (chain), statistics (chain_u)
+    if (chain) pbn2 = bn_ref(nullptr, 0, a->prev_g2, a->prev_b2);
+    if (chain_u) pbn2 = bn_ref(a->prev_stats, C, a->prev_g2, a->prev_b2);
+    HIP_TRY(launch_bn1_bwd_apply(a->dx, a->x, c.bn1, L.sd, L.sdn, add, N, C, T * V,
+                                 (int64_t)N * T * V, d->training, pbn2,
+                                 chain ? a->prev_sums : nullptr, chain_u ? a->prev_U : nullptr, s));
   }
   return STGCN_OK;
 }
@@ -984,10 +1004,8 @@ extern "C" int stgcn_block_bwd_dseed(const stgcn_desc_t *d, const stgcn_bwd_args
   c.res = residual(d);
   c.drop = make_dropout(d, a->dropout_p, a->seed, seed_dev);
   const int N = d->N, C = d->C_in, R = d->C_out, T = d->T, V = d->V, K = d->K;
-  c.mean1 = a->stats;
-  c.invstd1 = a->stats + C;
-  c.mean2 = a->stats + 2 * C;
-  c.invstd2 = a->stats + 2 * C + R;
+  c.bn1 = bn_ref(a->stats, C, a->g1, a->b1);
+  c.bn2 = bn_ref(a->stats + 2 * C, R, a->g2, a->b2);
   // deferred dx (ABI 5; bwd_spatial_dgrad)
   c.defer = d->need_dx && d->training && !c.res && a->prev_g2 && a->prev_b2 && a->prev_sums &&
             a->prev_U && a->prev_stats && a->x_stats && a->dx_coef && a->dx_deferred &&
@@ -1059,15 +1077,10 @@ struct TimedPlan {
   bool wgrad = false;
   // which 3 on the fused bf16 spatial forward (k_sp_fwd_bf16 / k_sp_fwd_wide)
   bool spf = false;
-  const float *x = nullptr, *st = nullptr, *A = nullptr, *W = nullptr, *biasZ = nullptr;
-  void *wpk = nullptr;
-  float *Z = nullptr;
-  __bf16 *Gk = nullptr;
+  SpatialFwd sf;
   // which 4: the spatial backward (5: its H GEMM only, 6: its joint kernel only)
   bool spb = false, spb_gemm = true, spb_joint = true;
-  const float *dZ = nullptr;
-  float *H = nullptr, *dx = nullptr, *dA = nullptr;
-  double *sd = nullptr;
+  SpatialBwd sb;
   // f16x2: the operands whose max |x| the fp16 splits scale by (computed once
   // before the timed launches, as the block does before its GEMMs)
   unsigned *amax = nullptr;
@@ -1120,11 +1133,7 @@ TimedPlan plan_timed(const stgcn_desc_t *d, int which, void *scratch) {
     if (fold_bna(d)) {  // x in: BN1 in the loader, the joint contraction in the epilogue
       p.bna = 1;
       p.sA = c.take<float>((size_t)V * V);
-      float *st = c.take<float>((size_t)4 * C);
-      p.mean1 = st;
-      p.invstd1 = st + C;
-      p.g1 = st + 2 * C;
-      p.b1 = st + 3 * C;
+      p.bn1 = bn_packed(c.take<float>((size_t)4 * C), C);
     }
     P.cp[P.ncp++] = p;
     // (bna: + the joint contraction 2 K C_out T V^2 of the spatial forward, now here)
@@ -1164,10 +1173,7 @@ TimedPlan plan_timed(const stgcn_desc_t *d, int which, void *scratch) {
         p.spb = 1;
         p.sx = sx;
         p.sA = sA;
-        p.mean1 = st;
-        p.invstd1 = st + C;
-        p.g1 = st + 2 * C;
-        p.b1 = st + 3 * C;
+        p.bn1 = bn_packed(st, C);
         p.sd = sd;
         p.sdn = sd + C;
         p.dA = dA;
@@ -1199,11 +1205,7 @@ TimedPlan plan_timed(const stgcn_desc_t *d, int which, void *scratch) {
     }
     if (fold_bna(d) && w.bf16 == 3) {  // P = dU A, Q = x with BN1 at staging
       // (taken whether or not scratch is given: the size query must match)
-      float *st = c.take<float>((size_t)4 * C);
-      w.q_mean = st;
-      w.q_invstd = st + C;
-      w.q_g = st + 2 * C;
-      w.q_b = st + 3 * C;
+      w.q_bn = bn_packed(c.take<float>((size_t)4 * C), C);
     }
     P.wp = w;
     P.wgrad = true;
@@ -1214,22 +1216,24 @@ TimedPlan plan_timed(const stgcn_desc_t *d, int which, void *scratch) {
     P.spb = true;
     P.spb_gemm = which != 6 && !fold;  // (folded: the data gradient wrote H)
     P.spb_joint = which != 5;
-    P.wpk = wpk;
-    P.x = c.take<float>((size_t)N * C * T * V);
-    P.st = c.take<float>((size_t)4 * C);
-    P.A = c.take<float>((size_t)K * V * V);
-    P.W = c.take<float>((size_t)K * R * C);
-    P.dZ = c.take<float>((size_t)N * R * T * V);
-    P.dx = c.take<float>((size_t)N * C * T * V);
-    P.dA = c.take<float>((size_t)K * V * V);
-    P.sd = c.take<double>((size_t)2 * C);
-    if (!fused_spb(d)) {
-      P.H = c.take<float>((size_t)N * K * C * T * V);
-    }
+    const float *x = c.take<float>((size_t)N * C * T * V);
+    const float *st = c.take<float>((size_t)4 * C);
+    const float *A = c.take<float>((size_t)K * V * V);
+    const float *W = c.take<float>((size_t)K * R * C);
+    const float *dZ = c.take<float>((size_t)N * R * T * V);
+    float *dx = c.take<float>((size_t)N * C * T * V);
+    float *dA = c.take<float>((size_t)K * V * V);
+    double *sd = c.take<double>((size_t)2 * C);
+    float *H = fused_spb(d) ? nullptr : c.take<float>((size_t)N * K * C * T * V);
     if (!fused_spb(d) && !fold) {
       const float *Wz = c.take<float>((size_t)R * K * C);  // (the packed W' of the block)
-      P.cp[P.ncp++] = h_gemm(d, P.dZ, Wz, P.H, wpk);
+      P.cp[P.ncp++] = h_gemm(d, dZ, Wz, H, wpk);
     }
+    P.sb = spatial_bwd(d, fused_spb(d) ? dZ : H, x, bn_packed(st, C), A, dx, dA, sd, sd + C);
+    P.sb.write_dx = 1;  // differs from the block without need_dx: dx is always written
+    P.sb.W = W;
+    P.sb.wpk = wpk;
+    P.sb.only = P.spb_gemm && P.spb_joint ? 0 : (P.spb_gemm ? 1 : 2);
     P.flops = (P.spb_gemm ? 2.0 * K * C * (double)R * T * V * N : 0.0) +
               (P.spb_joint ? 4.0 * K * C * (double)T * V * V * N : 0.0);
     if (fused_spb50(d) && which >= 5)  // k_sp50_dx / _dA: each its H GEMM + its contraction
@@ -1238,14 +1242,15 @@ TimedPlan plan_timed(const stgcn_desc_t *d, int which, void *scratch) {
     // the forward's fused spatial kernel (G kept in bf16 as in the stack)
     // differs from the block: a residual block's BN2 sums of Z are not taken
     P.spf = true;
-    P.wpk = wpk;
-    P.x = c.take<float>((size_t)N * C * T * V);
-    P.st = c.take<float>((size_t)4 * C);
-    P.A = c.take<float>((size_t)K * V * V);
-    P.W = c.take<float>((size_t)K * R * C);
-    P.biasZ = c.take<float>((size_t)R * V);
-    P.Z = c.take<float>((size_t)N * R * T * V);
-    P.Gk = reinterpret_cast<__bf16 *>(c.take<char>(sp_keep_g_bytes(N, C, T, V, K)));
+    const float *x = c.take<float>((size_t)N * C * T * V);
+    const float *st = c.take<float>((size_t)4 * C);
+    P.sf = spatial_fwd(d, x, bn_packed(st, C), c.take<float>((size_t)K * V * V));
+    P.sf.wpk = wpk;
+    P.sf.W = c.take<float>((size_t)K * R * C);
+    P.sf.biasZ = c.take<float>((size_t)R * V);
+    P.sf.Z = c.take<float>((size_t)N * R * T * V);
+    P.sf.z_bf16 = z_bf16(d) ? 1 : 0;
+    P.sf.Gk = reinterpret_cast<__bf16 *>(c.take<char>(sp_keep_g_bytes(N, C, T, V, K)));
     P.flops = 2.0 * K * C * (double)R * T * V * N + 2.0 * K * C * (double)T * V * V * N;
   } else {
     const float *G = c.take<float>((size_t)N * K * C * T * V);
@@ -1291,26 +1296,14 @@ int stgcn_time_kernel(const stgcn_desc_t *d, int which, void *scratch, size_t sc
   auto launch = [&]() -> hipError_t {
     if (P.wgrad) return launch_wgrad_taps(P.wp, s);
     if (P.spb) {
-      const int C = d->C_in;
-      if (fused_spb(d))
-        return launch_sp_bwd_fused(P.dZ, P.x, P.st, P.st + C, P.st + 2 * C, P.st + 3 * C, P.A,
-                                   P.W, P.wpk, P.dx, P.dA, P.sd, P.sd + C, d->N, C, d->C_out,
-                                   d->T, d->V, d->K, 1, residual(d) ? 1 : 0, s, nullptr,
-                                   P.spb_gemm && P.spb_joint ? 0 : (P.spb_gemm ? 1 : 2));
+      if (fused_spb(d)) return launch_sp_bwd_fused(P.sb, s);
       if (P.spb_gemm) {
         hipError_t e = launch_conv_gemm(P.cp[0], s);
         if (e != hipSuccess || !P.spb_joint) return e;
       }
-      return launch_spatial_dx(P.H, P.x, P.st, P.st + C, P.st + 2 * C, P.st + 3 * C, P.A, P.dx,
-                               P.dA, P.sd, P.sd + C, d->N, C, d->T, d->V, d->K, 1,
-                               residual(d) ? 1 : 0, bf16(d) ? 1 : 0, s);
+      return launch_spatial_dx(P.sb, s);
     }
-    if (P.spf) {
-      const int C = d->C_in;
-      return launch_sp_fwd_bf16(P.x, P.st, P.st + C, P.st + 2 * C, P.st + 3 * C, P.A, P.W,
-                                P.biasZ, P.wpk, P.Z, z_bf16(d) ? 1 : 0, P.Gk, nullptr, nullptr, d->N, C, d->C_out,
-                                d->T, d->V, d->K, residual(d) ? 1 : 0, s);
-    }
+    if (P.spf) return launch_sp_fwd_bf16(P.sf, s);
     for (int i = 0; i < P.ncp; ++i) {
       hipError_t e = launch_conv_gemm(P.cp[i], s);
       if (e != hipSuccess) return e;
@@ -1380,7 +1373,8 @@ int spatial_check(const stgcn_spatial_desc_t *sd, stgcn_desc_t *d) {
   return stgcn_check_desc(d);
 }
 
-hipError_t fill_identity_bn(float *ident, int C, hipStream_t s) {
+hipError_t fill_identity_bn(float *ident, int C, hipStream_t s, BnRef *bn) {
+  *bn = bn_packed(ident, C);
   hipError_t e = hipMemsetD32Async((hipDeviceptr_t)ident, 0u, (size_t)C, s);  // mean 0
   if (e == hipSuccess)  // invstd 1, gamma 1
     e = hipMemsetD32Async((hipDeviceptr_t)(ident + C), 0x3f800000u, (size_t)2 * C, s);
@@ -1416,16 +1410,18 @@ int stgcn_spatial_fwd(const stgcn_spatial_desc_t *sd, const float *x, const floa
   const SpatialLayout L = spatial_layout(d, workspace, false);
   if (!workspace || workspace_bytes < L.total) return fail(STGCN_E_INVALID, "workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  const int N = d->N, C = d->C_in, R = d->C_out, T = d->T, V = d->V, K = d->K;
-  HIP_TRY(fill_identity_bn(L.ident, C, s));
+  const int C = d->C_in, R = d->C_out, V = d->V, K = d->K;
+  BnRef ident;
+  HIP_TRY(fill_identity_bn(L.ident, C, s, &ident));
   HIP_TRY(launch_bias_rv(A, bW, L.biasZ, K, R, V, s));
   const float *Wz = W;
   if (K > 1) {
     HIP_TRY(launch_pack_w(W, L.Wpk, K, R, C, s));
     Wz = L.Wpk;
   }
-  HIP_TRY(launch_gather_fwd(x, L.ident, L.ident + C, L.ident + 2 * C, L.ident + 3 * C, A, L.G, N,
-                            C, T, V, K, 0, s));
+  SpatialFwd f = spatial_fwd(d, x, ident, A);
+  f.G = L.G;
+  HIP_TRY(launch_gather_fwd(f, s));
   HIP_TRY(launch_conv_gemm(spatial_gemm(d, L.G, Wz, out, L.biasZ, L.wpk), s));
   return STGCN_OK;
 }
@@ -1454,12 +1450,14 @@ int stgcn_spatial_bwd(const stgcn_spatial_desc_t *sd, const float *dout, const f
   if (!workspace || workspace_bytes < L.total) return fail(STGCN_E_INVALID, "workspace too small");
   hipStream_t s = (hipStream_t)stream;
   const int N = d->N, C = d->C_in, R = d->C_out, T = d->T, V = d->V, K = d->K;
-  HIP_TRY(fill_identity_bn(L.ident, C, s));
+  BnRef ident;
+  HIP_TRY(fill_identity_bn(L.ident, C, s, &ident));
   HIP_TRY(hipMemsetAsync(L.sd, 0, sizeof(double) * C, s));
   HIP_TRY(hipMemsetAsync(L.sdn, 0, sizeof(double) * C, s));
   HIP_TRY(hipMemsetAsync(L.SdZ, 0, sizeof(double) * R * V, s));
-  const float *mean = L.ident, *invstd = L.ident + C, *g = L.ident + 2 * C, *b = L.ident + 3 * C;
-  HIP_TRY(launch_gather_fwd(x, mean, invstd, g, b, A, L.G, N, C, T, V, K, 0, s));
+  SpatialFwd f = spatial_fwd(d, x, ident, A);
+  f.G = L.G;
+  HIP_TRY(launch_gather_fwd(f, s));
   {
     WgradParams w = wgrad_spatial(d, dout, L.G, L.slab);
     HIP_TRY(launch_wgrad(w, s));
@@ -1474,8 +1472,9 @@ int stgcn_spatial_bwd(const stgcn_spatial_desc_t *sd, const float *dout, const f
   }
   HIP_TRY(launch_conv_gemm(h_gemm(d, dout, Wz, L.H, L.wpk), s));
   // dx = sum_k H_k A_k (BatchNorm identity: dx is dxhat; sd/sdn unused)
-  HIP_TRY(launch_spatial_dx(L.H, x, mean, invstd, g, b, A, dx, dA, L.sd, L.sdn, N, C, T, V, K,
-                            dx != nullptr, 0, bf16(d) ? 1 : 0, s));
+  SpatialBwd b = spatial_bwd(d, L.H, x, ident, A, dx, dA, L.sd, L.sdn);
+  b.write_dx = dx != nullptr;
+  HIP_TRY(launch_spatial_dx(b, s));
   return STGCN_OK;
 }
 

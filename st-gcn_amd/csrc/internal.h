@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
 
 namespace stgcn {
 
@@ -48,14 +49,26 @@ __device__ __forceinline__ Dropout dropout_resolve(Dropout d) {
   return d;
 }
 
+// One BatchNorm as the kernels read it: per-channel statistics and affine pair.
+// A member of the kernel-argument structs below, where four pointers stood.
+struct BnRef {
+  const float *mean = nullptr, *invstd = nullptr, *g = nullptr, *b = nullptr;
+};
+// ... from a packed [mean | invstd | g | b] table of 4 * C floats
+inline BnRef bn_packed(const float *t, int C) { return {t, t + C, t + 2 * C, t + 3 * C}; }
+// ... from the statistics [mean | invstd] over C channels, gamma and beta
+inline BnRef bn_ref(const float *stats, int C, const float *g, const float *b) {
+  return {stats, stats + C, g, b};
+}
+
 // Deferred-dx chain (ABI 5; capi.hip "deferred dx"): the spatial backward of
 // block i reads the PREVIOUS block's pre-BN2 tensor U in place of its input x
 // and rebuilds x = ReLU((U - mean) * invstd * g + b) exactly as that block's
 // output pass did; with the mask m = x > 0 and uhat = (U - mean) * invstd it
-// adds s1[c] += sum m * dxhat, s2[c] += sum m * dxhat * uhat (fp64). mean ==
+// adds s1[c] += sum m * dxhat, s2[c] += sum m * dxhat * uhat (fp64). bn.mean ==
 // nullptr: off (x read as is).
 struct PrevBn {
-  const float *mean = nullptr, *invstd = nullptr, *g = nullptr, *b = nullptr;
+  BnRef bn;
   double *s1 = nullptr, *s2 = nullptr;
 };
 
@@ -115,12 +128,13 @@ struct ConvGemmParams {
   // spb (the folded block's data gradient, V = 18, K = 1; kernels_x3.hip
   // spb_epilogue): the tile holds H = W'^T dZ (rows = input channels). Instead of
   // storing H the epilogue forms dxhat = H A (stored to out, null: not stored),
-  // the BN1 backward sums sd / sdn (and, prev.mean set, the deferred-dx chain's
+  // the BN1 backward sums sd / sdn (and, prev.bn.mean set, the deferred-dx chain's
   // s1 / s2 over the previous block's U read from sx) and dA += H^T BN1(x):
   // the SpatialConv backward never round-trips H through HBM.
   int spb;
   int sd_given;  // sd already holds sum dxhat (launch_fold_small_sd): the epilogue adds only sdn
-  const float *sx, *sA, *mean1, *invstd1, *g1, *b1;
+  const float *sx, *sA;
+  BnRef bn1;
   PrevBn prev;
   double *sd, *sdn;
   float *dA;
@@ -132,7 +146,7 @@ struct ConvGemmParams {
   // wpk already holds the packed split planes of w (stgcn_fold_prep): no pack launch
   int wpk_ready;
   // bna (with f16x2, V = 18, the folded block's forward; kernels_x3.hip): in[] is
-  // the block input x, BN1 (mean1, invstd1, g1, b1) is applied in the window
+  // the block input x, BN1 (bn1) is applied in the window
   // loader and the joint contraction with sA in the epilogue -- G is never formed;
   // amax_in holds max |x| (the fp16 operand bound is formed in the kernel)
   int bna;
@@ -162,10 +176,10 @@ struct WgradParams {
   // power-of-two-scaled P / Q; amax_p / amax_q: device max |P| / max |Q| bits
   int f16x2;
   const unsigned *amax_p, *amax_q;
-  // (f16x2 only) Q is the block input x of the folded block: BN1 (q_mean,
-  // q_invstd, q_g, q_b) is applied while staging Q (0 in padded frames), amax_q
+  // (f16x2 only) Q is the block input x of the folded block: BN1 (q_bn;
+  // q_bn.mean null: off) is applied while staging Q (0 in padded frames), amax_q
   // holds max |x|; P is dU contracted with A (dU A), so the product is dWc
-  const float *q_mean, *q_invstd, *q_g, *q_b;
+  BnRef q_bn;
   int x3_mr;  // k_wgrad_x3 row tiles of 64 x_mr rows (2: with f16x2 only; set by plan_wgrad_x3)
 };
 
@@ -222,25 +236,35 @@ hipError_t launch_fold_prep(const FoldPrepSpec *specs, int n, hipStream_t s);
 hipError_t launch_fold_grads(const float *slab, int S, const float *scratch, const float *bZ,
                              const double *Tq, int R, int C, int V, float *dwc, float *dWt,
                              float *dW, hipStream_t s);
-// k_bn_relu_bwd_apply that also writes the clip-chunk sums of dU,
-// cs[z][C][L] for z < apply_cols_chunks(N) (kernels_bn.hip)
+// The ReLU + BN2 backward (kernels_bn.hip), one descriptor for its passes over
+// U (N, C, L), g = dy on the mask of y = ReLU(BN2(U)):
+//   _reduce      sg[c] = sum g, sgu[c] = sum g uhat, into its arguments
+//   _apply       dU from sg / sgu, sdu[c] += sum dU
+//   _apply_cols  ... and the clip-chunk sums of dU, cs[z][C][L] for
+//                z < apply_cols_chunks(N); amax (or null): max |dU|
+//   _apply_fr    ... frame-wise (V = 18, L = T_out * V), also dUA = dU A (the folded
+//                block without G, capi.hip fold_bna) and max |dU|, max |dUA| (amaxa)
+struct Bn2Bwd {
+  // dy_nc (ABI 10, stgcn_bwd_args_t.dy_nc): dy[n, c, :] == dy_nc[n * C + c], no dy
+  // tensor is read (not by _apply_fr)
+  const float *dy = nullptr, *dy_nc = nullptr, *U = nullptr;
+  BnRef bn;
+  const double *sg = nullptr, *sgu = nullptr;
+  float *dU = nullptr, *dUA = nullptr;
+  double *sdu = nullptr, *cs = nullptr;
+  int N = 0, C = 0, L = 0, V = 0;
+  int training = 1;  // 0: eval-mode BatchNorm backward (no batch-mean terms)
+  Dropout drop;
+  int du_bf16 = 0;  // dU stored as bf16 in its fp32 buffer (_apply, _apply_cols)
+  const float *dy_coef = nullptr;  // deferred-dx chain (below): dy is the next block's dxhat
+  unsigned *amax = nullptr, *amaxa = nullptr;
+  const float *A = nullptr;
+};
 int apply_cols_chunks(int N);
-hipError_t launch_bn_relu_bwd_apply_cols(const float *dy, const float *U, const float *mean,
-                                         const float *invstd, const float *g, const float *b,
-                                         const double *sg, const double *sgu, float *dU,
-                                         double *sdu, int N, int C, int L, int training,
-                                         Dropout drop, hipStream_t s, int du_bf16,
-                                         const float *dy_coef, double *cs,
-                                         unsigned *amax = nullptr, const float *dync = nullptr);
-// ... frame-wise (V = 18), also writing dUA = dU A (the folded block without G,
-// capi.hip fold_bna) and the fp16 operand bounds max |dU| (amax), max |dUA| (amaxa)
-hipError_t launch_bn_relu_bwd_apply_fr(const float *dy, const float *U, const float *mean,
-                                       const float *invstd, const float *g, const float *b,
-                                       const double *sg, const double *sgu, float *dU, float *dUA,
-                                       double *sdu, int N, int C, int To, int V, int training,
-                                       Dropout drop, const float *dy_coef, double *cs,
-                                       unsigned *amax, unsigned *amaxa, const float *A,
-                                       hipStream_t s);
+hipError_t launch_bn_relu_bwd_reduce(const Bn2Bwd &q, double *sg, double *sgu, hipStream_t s);
+hipError_t launch_bn_relu_bwd_apply(const Bn2Bwd &q, hipStream_t s);
+hipError_t launch_bn_relu_bwd_apply_cols(const Bn2Bwd &q, hipStream_t s);
+hipError_t launch_bn_relu_bwd_apply_fr(const Bn2Bwd &q, hipStream_t s);
 // bf16 path (kernels_bf16.hip): the reference's graphs (V = 18, 25, 50) with
 // the fp32 path's tile plan (FT = kTileCols / V); launch_conv_gemm dispatches here
 // when p.bf16 and conv_bf16_supported(p).
@@ -321,49 +345,34 @@ hipError_t launch_bn_finalize(const double *sum, const double *sq, int C, int64_
 // uhat = (U - mean) * invstd, cnt += sum m, su += sum m * uhat, xu += sum y * uhat
 // (the deferred-dx chain's forward sums)
 // ymax (or null): max y as float bits (block_amax): the next block's operand bound
-hipError_t launch_bn_relu_fwd(const float *U, const float *mean, const float *invstd,
-                              const float *g, const float *b, float *y, int N, int C, int L,
+hipError_t launch_bn_relu_fwd(const float *U, const BnRef &bn, float *y, int N, int C, int L,
                               double *ysum, double *ysq, Dropout drop, hipStream_t s,
                               double *yext = nullptr, unsigned *ymax = nullptr);
-hipError_t launch_bn_relu_bwd_reduce(const float *dy, const float *U, const float *mean,
-                                     const float *invstd, const float *g, const float *b,
-                                     int N, int C, int L, double *sg, double *sgu, Dropout drop,
-                                     hipStream_t s, const float *dync = nullptr);
-hipError_t launch_bn_relu_bwd_apply(const float *dy, const float *U, const float *mean,
-                                    const float *invstd, const float *g, const float *b,
-                                    const double *sg, const double *sgu, float *dU,
-                                    double *sdu, int N, int C, int L, int training,
-                                    Dropout drop, hipStream_t s, int du_bf16 = 0,
-                                    const float *dy_coef = nullptr, const float *dync = nullptr);
-// (dync non-null, ABI 10 stgcn_bwd_args_t.dy_nc: dy[n, c, :] == dync[n * C + c];
-// the three ReLU + BN2 backward passes then read no dy tensor)
 // Deferred-dx chain: block i's BN1 backward folded into block i-1's ReLU+BN2
 // backward. dy_coef (5*C: [a | md | mu | is | mdn], launch_chain_coef) makes
 // launch_bn_relu_bwd_apply read dy as the next block's dxhat and form
 //   dy = a * (dxhat - md - (y - mu) * is * mdn),  y = ReLU((U - mean) * invstd * g + b)
 // (k_bn1_bwd_apply's arithmetic) instead of reading a materialised dy.
 // launch_chain_coef (block i, C = its C_in): from its BN1 sums sd / sdn, its BN1
-// statistics (mean1, invstd1, g1), the prev-mode sums s1 / s2 of its spatial
+// statistics (bn1: mean, invstd, g), the prev-mode sums s1 / s2 of its spatial
 // backward and xst (5*C: the previous block's output sums [sum | sumsq | cnt |
 // su | xu]) -> dg1 = sdn, db1 = sd, coef (5*C) and psum (2*C: the previous
 // block's [sum m dy | sum m dy uhat]). M = N*T*V.
-hipError_t launch_chain_coef(const double *sd, const double *sdn, const float *mean1,
-                             const float *invstd1, const float *g1, const double *s1,
-                             const double *s2, const double *xst, int C, int64_t M,
-                             float *dg1, float *db1, float *coef, double *psum, hipStream_t s);
+hipError_t launch_chain_coef(const double *sd, const double *sdn, const BnRef &bn1,
+                             const double *s1, const double *s2, const double *xst, int C,
+                             int64_t M, float *dg1, float *db1, float *coef, double *psum,
+                             hipStream_t s);
 hipError_t launch_bn_grads_out(const double *sg, const double *sgu, const double *sdu, int C,
                                float *dgamma, float *dbeta, float *dbias, hipStream_t s);
 // add (same layout as dx, or null) is added after the BN1 backward (residual path)
 // training = 0: eval-mode BatchNorm backward (running statistics are constants)
-// pg2/pb2/psum (or null): also the previous block's ReLU+BN2 backward sums;
-// pU/pmean/pinvstd (or null): that block's pre-BN2 tensor and statistics, read
-// for channels where uhat = (x - b2) / g2 is ill-conditioned
-hipError_t launch_bn1_bwd_apply(float *dx, const float *x, const float *mean,
-                                const float *invstd, const float *g, const double *sd,
+// pbn2.g / .b and psum (or null): also the previous block's ReLU+BN2 backward sums;
+// pU and pbn2.mean / .invstd (or null): that block's pre-BN2 tensor and
+// statistics, read for channels where uhat = (x - b2) / g2 is ill-conditioned
+hipError_t launch_bn1_bwd_apply(float *dx, const float *x, const BnRef &bn1, const double *sd,
                                 const double *sdn, const float *add, int N, int C, int L,
-                                int64_t M, int training, const float *pg2, const float *pb2,
-                                double *psum, const float *pU, const float *pmean,
-                                const float *pinvstd, hipStream_t s);
+                                int64_t M, int training, const BnRef &pbn2, double *psum,
+                                const float *pU, hipStream_t s);
 // dout = dy * (y > 0) (the final ReLU of the residual block), sum[c] += sum dout
 // (with dropout: y is the dropped output; dout = dy * scale where y > 0)
 hipError_t launch_relu_bwd(const float *dy, const float *y, float *dout, double *sum, int N,
@@ -373,40 +382,85 @@ hipError_t launch_relu_bwd(const float *dy, const float *y, float *dout, double 
 hipError_t launch_pack_w(const float *W, float *Wpk, int K, int R, int C, hipStream_t s);
 hipError_t launch_bias_rv(const float *A, const float *bW, float *bias_rv, int K, int R, int V,
                           hipStream_t s);
-// G = f(BN1(x)) A^T with f = identity, or ReLU when relu != 0 (residual block)
-// amax (or null): max |G| as float bits (atomicMax; zeroed by the caller), the
-// f16x2 operand bound of the folded temporal GEMMs
 // BN statistics from per-tile partials [2][C][ntiles] (ConvGemmParams.stat_part):
 // one workgroup per channel, fixed summation order
 hipError_t launch_bn_finalize_parts(const double *part, int ntiles, int C, int64_t M, float eps,
                                     float momentum, int training, float *rm, float *rv,
                                     float *mean_out, float *invstd_out, hipStream_t s,
                                     double *ys_zero = nullptr, int nw = 0);
-hipError_t launch_gather_fwd(const float *x, const float *mean, const float *invstd,
-                             const float *g, const float *b, const float *A, float *G, int N,
-                             int C, int T, int V, int K, int relu, hipStream_t s,
-                             unsigned *amax = nullptr, const PrevBn *pv = nullptr);
-// pv (x = ReLU(BN2_prev(U)) from the previous block's U, ABI 8) runs on
-// k_gather4 only: K = 1, 16-byte aligned x / G and these shapes
+// The runtime joint count as a compile-time constant: f(std::integral_constant<int, V>)
+// for V = 18, 25 and, for every other value, 50 (the caller has checked the joint count)
+template <class F>
+inline auto dispatch_v(int V, F &&f) {
+  if (V == 18) return f(std::integral_constant<int, 18>{});
+  if (V == 25) return f(std::integral_constant<int, 25>{});
+  return f(std::integral_constant<int, 50>{});
+}
+
+// The spatial forward family, one descriptor (block_plan.h spatial_fwd), with
+// f = ReLU when relu (residual block), else the identity:
+//   launch_gather_fwd   G = f(BN1(x)) A^T in fp32; amax (or null): max |G| as float
+//                       bits (atomicMax; zeroed by the caller), the f16x2 operand
+//                       bound of the folded temporal GEMMs
+//   launch_sp_fwd_bf16  Z = W' (f(BN1(x)) A^T) + biasZ, kernels_fused.hip (below);
+//                       Gk, ssum / ssq or null
+struct SpatialFwd {
+  const float *x = nullptr;
+  BnRef bn;
+  const float *A = nullptr;
+  int N = 0, C = 0, R = 0, T = 0, V = 0, K = 0, relu = 0;
+  // prev.bn.mean set (ABI 8): x holds the previous block's U and the input is
+  // ReLU(BN2_prev(U)). launch_gather_fwd: on k_gather4 only -- K = 1, 16-byte
+  // aligned x / G and gather_prev_supported shapes
+  PrevBn prev;
+  float *G = nullptr;
+  unsigned *amax = nullptr;
+  const float *W = nullptr, *biasZ = nullptr;
+  void *wpk = nullptr;
+  float *Z = nullptr;
+  int z_bf16 = 0;
+  __bf16 *Gk = nullptr;
+  double *ssum = nullptr, *ssq = nullptr;
+};
+hipError_t launch_gather_fwd(const SpatialFwd &f, hipStream_t s);
 bool gather_prev_supported(int C, int T, int V);
 hipError_t launch_sum_nt(const float *X, int N, int C, int T, int V, double *out,
                          hipStream_t s);
 hipError_t launch_spatial_small(const double *SdZ, const float *A, const float *bW, int K,
                                 int R, int V, float *dbW, float *dA, hipStream_t s);
-hipError_t launch_spatial_dx(const float *H, const float *x, const float *mean,
-                             const float *invstd, const float *g, const float *b,
-                             const float *A, float *dx, float *dA, double *sd, double *sdn,
-                             int N, int C, int T, int V, int K, int write_dx, int relu,
-                             int bf16ops, hipStream_t s, const PrevBn *prev = nullptr,
-                             float *dA_part = nullptr, int64_t part_cap = 0,
-                             int64_t *nparts = nullptr);
+// The spatial backward family, one descriptor (block_plan.h spatial_bwd):
+//   launch_spatial_dx    from in = H = W'^T dZ: dx = sum_k H_k A_k, dA, BN1 sums
+//   launch_sp_bwd_fused  from in = dZ, H never in HBM, kernels_spbwd.hip (below)
+struct SpatialBwd {
+  const float *in = nullptr, *x = nullptr;
+  BnRef bn;
+  const float *A = nullptr;
+  float *dx = nullptr, *dA = nullptr;
+  double *sd = nullptr, *sdn = nullptr;
+  int N = 0, C = 0, R = 0, T = 0, V = 0, K = 0, write_dx = 0, relu = 0;
+  PrevBn prev;  // prev.bn.mean set: x holds the previous block's U (deferred dx)
+  // launch_spatial_dx. bf16ops: at V = 50 the two-plane k_spatial_bwd6 of the bf16
+  // blocks. dA_part (or null: fp32 atomics into dA): part_cap slots of K V V floats
+  // for the joint kernel's per-workgroup partials; *nparts: how many it wrote (0:
+  // it took none), for launch_dA_reduce
+  int bf16ops = 0;
+  float *dA_part = nullptr;
+  int64_t part_cap = 0, *nparts = nullptr;
+  // launch_sp_bwd_fused. wpk: scratch of sp_bwd_fused_wpk_bytes. V = 50 runs as two
+  // kernels (k_sp50_dx, k_sp50_dA); only = 1 / 2 launches just the first / second
+  // of them (timing entry point), 0 both
+  const float *W = nullptr;
+  void *wpk = nullptr;
+  int only = 0;
+};
+hipError_t launch_spatial_dx(const SpatialBwd &b, hipStream_t s);
 int conv_x3_tile_rows(const ConvGemmParams &p, int npl);
 // Deterministic dA: adds nparts partials part[i][n] (i in order) to dA[n], in two
 // fixed-order passes (lvl: kDaLvl * n doubles of scratch)
 constexpr int kDaLvl = 64;
 hipError_t launch_dA_reduce(const float *part, int64_t nparts, int n, double *lvl, float *dA,
                             hipStream_t s);
-// launch_spatial_dx takes a PrevBn for this shape (its k_spatial_bwd5 / _bwd6
+// launch_spatial_dx runs prev mode for this shape (its k_spatial_bwd5 / _bwd6
 // paths; 16-byte aligned tensors assumed, as torch allocates them)
 bool spatial_dx_prev_supported(int N, int C, int T, int V, int K);
 
@@ -417,12 +471,7 @@ bool spatial_dx_prev_supported(int N, int C, int T, int V, int K);
 bool sp_fwd_bf16_supported(int C, int V, int K, int R, bool residual);
 size_t sp_fwd_bf16_wpk_bytes(int C, int R, int K, int V);  // packed W' + A image
 size_t sp_keep_g_bytes(int N, int C, int T, int V, int K);
-hipError_t launch_sp_fwd_bf16(const float *x, const float *mean, const float *invstd,
-                              const float *g, const float *b, const float *A, const float *W,
-                              const float *biasZ, void *wpk, float *Z, int z_bf16, __bf16 *Gk,
-                              double *ssum,
-                              double *ssq, int N, int C, int R, int T, int V, int K, int relu,
-                              hipStream_t s, const PrevBn *prev = nullptr);
+hipError_t launch_sp_fwd_bf16(const SpatialFwd &f, hipStream_t s);
 // dW' = dZ Gk^T from the kept bf16 G (P = dZ fp32, Q = Gk, C = K*C_in).
 void plan_wgrad_gk(WgradParams &w, int T);
 hipError_t launch_wgrad_gk(const WgradParams &p, hipStream_t s);
@@ -433,13 +482,6 @@ hipError_t launch_wgrad_gk(const WgradParams &p, hipStream_t s);
 // sp_bwd_fused_wpk_bytes (packed W' + the A image).
 bool sp_bwd_fused_supported(int C, int V, int K, int R, int T);
 size_t sp_bwd_fused_wpk_bytes(int C, int R, int K, int V);
-hipError_t launch_sp_bwd_fused(const float *dZ, const float *x, const float *mean,
-                               const float *invstd, const float *g, const float *b,
-                               const float *A, const float *W, void *wpk, float *dx, float *dA,
-                               double *sd, double *sdn, int N, int C, int R, int T, int V, int K,
-                               int write_dx, int relu, hipStream_t s,
-                               const PrevBn *prev = nullptr, int only = 0);
-// V = 50 runs the fused backward as two kernels (k_sp50_dx, k_sp50_dA); only = 1 / 2
-// launches just the first / second of them (timing entry point), 0 both.
+hipError_t launch_sp_bwd_fused(const SpatialBwd &b, hipStream_t s);
 
 }  // namespace stgcn

@@ -175,7 +175,7 @@ __global__ __launch_bounds__(256) void k_gather3(const float *__restrict__ x,
 // they arrive by 16-byte LDS-DMA, each thread contracts its row from LDS (A in
 // LDS), and the outputs leave through LDS as float4 stores. (A persistent,
 // double-buffered variant measured slower: fewer workgroups per CU.)
-// pv.mean non-null (ABI 8, STGCN_PLAN_X_FROM_U): x holds the previous block's U
+// pv.bn.mean non-null (ABI 8, STGCN_PLAN_X_FROM_U): x holds the previous block's U
 // and the input is ReLU(BN2_prev(U)), formed as k_bn_relu_fwd forms its y.
 template <int V>
 __global__ __launch_bounds__(256) void k_gather4(const float *__restrict__ x,
@@ -210,9 +210,9 @@ __global__ __launch_bounds__(256) void k_gather4(const float *__restrict__ x,
   const int64_t n0 = r0 / CT, rem0 = r0 - n0 * CT;
   const int ci = (int)((rem0 + tid) / T);
   const float mu = mean[ci], a = invstd[ci] * g[ci], be = b[ci];
-  const bool prev = pv.mean != nullptr;
-  const float pmu = prev ? pv.mean[ci] : 0.f, pa = prev ? pv.invstd[ci] * pv.g[ci] : 0.f;
-  const float pbe = prev ? pv.b[ci] : 0.f;
+  const bool prev = pv.bn.mean != nullptr;
+  const float pmu = prev ? pv.bn.mean[ci] : 0.f, pa = prev ? pv.bn.invstd[ci] * pv.bn.g[ci] : 0.f;
+  const float pbe = prev ? pv.bn.b[ci] : 0.f;
   __syncthreads();
   float xv[VP];
 #pragma unroll
@@ -478,7 +478,7 @@ __global__ __launch_bounds__(bwd5_nw(KMAX) * 64) void k_spatial_bwd5(
   const int BUF = (K + 1) * PL;  // one buffer: K H planes + x plane (prev mode: U)
   float *dxs = smem + 2 * BUF;   // [RB][V]: reduction half 0, then dx
   float *dxs2 = dxs + PL;        // [RB][V]: reduction half 1 (NH == 2)
-  const bool pv = prev.mean != nullptr;
+  const bool pv = prev.bn.mean != nullptr;
   const int ns = pv ? 4 : 2;
   double *const gdst[4] = {sd, sdn, prev.s1, prev.s2};
   float *dred = dxs + NH * PL;   // [K][DW][DW]
@@ -599,8 +599,8 @@ __global__ __launch_bounds__(bwd5_nw(KMAX) * 64) void k_spatial_bwd5(
       const int seg = n0 * C + ci - cfirst;
       const BnAff bn1 = bn_aff(mean, invstd, g, b, ci);
       // prev mode: the staged plane is the previous block's U
-      const float pmu = pv ? prev.mean[ci] : 0.f, pis = pv ? prev.invstd[ci] : 1.f;
-      const float pa = pv ? pis * prev.g[ci] : 1.f, pb = pv ? prev.b[ci] : 0.f;
+      const float pmu = pv ? prev.bn.mean[ci] : 0.f, pis = pv ? prev.bn.invstd[ci] : 1.f;
+      const float pa = pv ? pis * prev.bn.g[ci] : 1.f, pb = pv ? prev.bn.b[ci] : 0.f;
       float sv[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int j = 0; j < (V + TPR - 1) / TPR; ++j) {
@@ -713,23 +713,21 @@ static size_t bwd5_lds(int K) {
   return sizeof(float) * ((size_t)(2 * (K + 1) + nh) * PL + (size_t)K * DW * DW);
 }
 
+// (dry: whether the kernel takes the shape; nothing but b's shape is read)
 template <int V, int RB, int KT>
-static bool launch_bwd5(const float *H, const float *x, const float *mean, const float *invstd,
-                        const float *g, const float *b, const float *A, float *dx, float *dA,
-                        double *sd, double *sdn, int C, int T, int K, int64_t rows,
-                        int write_dx, int relu, hipStream_t s, const PrevBn &prev,
-                        bool dry = false, float *dA_part = nullptr, int64_t part_cap = 0,
-                        int64_t *nparts = nullptr) {
-  const size_t lds = bwd5_lds<V, RB>(K);
-  if (lds > 160 * 1024 - 1024 || ((int64_t)C * T) % RB != 0 || rows >= (int64_t)1 << 31) return false;
+static bool launch_bwd5(const SpatialBwd &b, int64_t rows, bool dry, hipStream_t s) {
+  const size_t lds = bwd5_lds<V, RB>(b.K);
+  if (lds > 160 * 1024 - 1024 || ((int64_t)b.C * b.T) % RB != 0 || rows >= (int64_t)1 << 31)
+    return false;
   const int per_cu = std::max(1, std::min(8, (int)((160 * 1024) / (lds + 1024))));
   const dim3 grid((unsigned)std::min<int64_t>(rows / RB, 256 * per_cu));
-  if (K != KT) return false;
+  if (b.K != KT) return false;
   if (dry) return true;
-  float *part = dA_part && (int64_t)grid.x <= part_cap ? dA_part : nullptr;
-  if (part && nparts) *nparts = grid.x;
-  hipLaunchKernelGGL((k_spatial_bwd5<V, RB, KT>), grid, dim3(bwd5_nw(KT) * 64), lds, s, H, x, mean, invstd, g,
-                     b, A, dx, dA, sd, sdn, C, T, K, rows, write_dx, relu, prev, part);
+  float *part = b.dA_part && (int64_t)grid.x <= b.part_cap ? b.dA_part : nullptr;
+  if (part && b.nparts) *b.nparts = grid.x;
+  hipLaunchKernelGGL((k_spatial_bwd5<V, RB, KT>), grid, dim3(bwd5_nw(KT) * 64), lds, s, b.in, b.x,
+                     b.bn.mean, b.bn.invstd, b.bn.g, b.bn.b, b.A, b.dx, b.dA, b.sd, b.sdn, b.C, b.T,
+                     b.K, rows, b.write_dx, b.relu, b.prev, part);
   return true;
 }
 
@@ -766,7 +764,7 @@ __global__ __launch_bounds__(512, 1) void k_spatial_bwd6(
   const int BUF = (K + 1) * PL;  // one buffer: K H planes + x plane (prev mode: U)
   float *dxs = smem + 2 * BUF;   // [RB][V]: reduction half 0, then dx
   float *dxs2 = dxs + PL;        // [RB][V]: reduction half 1
-  const bool pv = prev.mean != nullptr;
+  const bool pv = prev.bn.mean != nullptr;
   const int ns = pv ? 4 : 2;
   double *const gdst[4] = {sd, sdn, prev.s1, prev.s2};
   // f(BN1(x)) split into 3 bf16 planes, joint-major [w][row] (pitch XTP: 16-byte
@@ -883,8 +881,8 @@ __global__ __launch_bounds__(512, 1) void k_spatial_bwd6(
       const int ci = rem / T;
       const int seg = n0 * C + ci - cfirst;
       const BnAff bn1 = bn_aff(mean, invstd, g, b, ci);
-      const float pmu = pv ? prev.mean[ci] : 0.f, pis = pv ? prev.invstd[ci] : 1.f;
-      const float pa = pv ? pis * prev.g[ci] : 1.f, pb = pv ? prev.b[ci] : 0.f;
+      const float pmu = pv ? prev.bn.mean[ci] : 0.f, pis = pv ? prev.bn.invstd[ci] : 1.f;
+      const float pa = pv ? pis * prev.bn.g[ci] : 1.f, pb = pv ? prev.bn.b[ci] : 0.f;
       float sv[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int j = 0; j < (V + TPR - 1) / TPR; ++j) {
@@ -1005,24 +1003,21 @@ __global__ __launch_bounds__(512, 1) void k_spatial_bwd6(
 }
 
 template <int V, int KT, bool BF>
-static bool launch_bwd6(const float *H, const float *x, const float *mean, const float *invstd,
-                        const float *g, const float *b, const float *A, float *dx, float *dA,
-                        double *sd, double *sdn, int C, int T, int K, int64_t rows,
-                        int write_dx, int relu, hipStream_t s, const PrevBn &prev,
-                        bool dry = false, float *dA_part = nullptr, int64_t part_cap = 0,
-                        int64_t *nparts = nullptr) {
+static bool launch_bwd6(const SpatialBwd &b, int64_t rows, bool dry, hipStream_t s) {
   constexpr int RB = 64;
   constexpr int PL = (RB * V + 255) / 256 * 256;
-  const size_t lds = sizeof(float) * ((size_t)(2 * (K + 1) + 2) * PL) + 3 * (size_t)V * (RB + 8) * 2;
-  if (K != KT || lds > 160 * 1024 - 1024 || ((int64_t)C * T) % RB != 0 ||
+  const size_t lds =
+      sizeof(float) * ((size_t)(2 * (b.K + 1) + 2) * PL) + 3 * (size_t)V * (RB + 8) * 2;
+  if (b.K != KT || lds > 160 * 1024 - 1024 || ((int64_t)b.C * b.T) % RB != 0 ||
       rows >= (int64_t)1 << 31)
     return false;
   if (dry) return true;
   const dim3 grid((unsigned)std::min<int64_t>(rows / RB, 256));
-  float *part = dA_part && 2 * (int64_t)grid.x <= part_cap ? dA_part : nullptr;
-  if (part && nparts) *nparts = 2 * (int64_t)grid.x;
-  hipLaunchKernelGGL((k_spatial_bwd6<V, KT, BF>), grid, dim3(512), lds, s, H, x, mean, invstd, g, b,
-                     A, dx, dA, sd, sdn, C, T, K, rows, write_dx, relu, prev, part);
+  float *part = b.dA_part && 2 * (int64_t)grid.x <= b.part_cap ? b.dA_part : nullptr;
+  if (part && b.nparts) *b.nparts = 2 * (int64_t)grid.x;
+  hipLaunchKernelGGL((k_spatial_bwd6<V, KT, BF>), grid, dim3(512), lds, s, b.in, b.x, b.bn.mean,
+                     b.bn.invstd, b.bn.g, b.bn.b, b.A, b.dx, b.dA, b.sd, b.sdn, b.C, b.T, b.K, rows,
+                     b.write_dx, b.relu, b.prev, part);
   return true;
 }
 
@@ -1114,20 +1109,23 @@ __global__ __launch_bounds__(256, 2) void k_gather_mfma(
 }
 
 template <int V, int KT>
-static bool launch_gather_mfma(const float *x, const float *mean, const float *invstd,
-                               const float *g, const float *b, const float *A, float *G, int C,
-                               int T, int K, int64_t rows, int relu, hipStream_t s) {
+static bool launch_gather_mfma_k(const SpatialFwd &f, int64_t rows, hipStream_t s) {
   constexpr int NT = (V + 31) / 32;
   constexpr int RB = 128 / NT;
   constexpr int PL = (RB * V + 255) / 256 * 256;
-  if (K != KT || ((int64_t)C * T) % RB != 0 || (RB * V) % 4 != 0 || rows >= (int64_t)1 << 31)
+  if (f.K != KT || ((int64_t)f.C * f.T) % RB != 0 || (RB * V) % 4 != 0 ||
+      rows >= (int64_t)1 << 31)
     return false;
-  const size_t lds = sizeof(float) * (size_t)(2 + K) * PL;
+  const size_t lds = sizeof(float) * (size_t)(2 + f.K) * PL;
   const int per_cu = std::max(1, std::min(2, (int)((160 * 1024) / (lds + 512))));
   const dim3 grid((unsigned)std::min<int64_t>(rows / RB, 256 * per_cu));
-  hipLaunchKernelGGL((k_gather_mfma<V, KT>), grid, dim3(256), lds, s, x, mean, invstd, g, b, A, G,
-                     C, T, K, rows, relu);
+  hipLaunchKernelGGL((k_gather_mfma<V, KT>), grid, dim3(256), lds, s, f.x, f.bn.mean, f.bn.invstd,
+                     f.bn.g, f.bn.b, f.A, f.G, f.C, f.T, f.K, rows, f.relu);
   return true;
+}
+template <int V>
+static bool launch_gather_mfma(const SpatialFwd &f, int64_t rows, hipStream_t s) {
+  return launch_gather_mfma_k<V, 2>(f, rows, s) || launch_gather_mfma_k<V, 3>(f, rows, s);
 }
 
 static int bwd3_rows(int V, int K) {
@@ -1143,53 +1141,39 @@ bool gather_prev_supported(int C, int T, int V) {
          sizeof(float) * ((size_t)2 * 256 * V + (size_t)V * ((V + 3) & ~3)) <= 160 * 1024;
 }
 
-hipError_t launch_gather_fwd(const float *x, const float *mean, const float *invstd,
-                             const float *g, const float *b, const float *A, float *G, int N,
-                             int C, int T, int V, int K, int relu, hipStream_t s, unsigned *amax,
-                             const PrevBn *pv) {
-  const PrevBn pvb = pv ? *pv : PrevBn{};
-  if (pv && (K != 1 || !gather_prev_supported(C, T, V) || ((uintptr_t)x & 15) != 0 ||
-             ((uintptr_t)G & 15) != 0))
+hipError_t launch_gather_fwd(const SpatialFwd &f, hipStream_t s) {
+  const int C = f.C, T = f.T, V = f.V, K = f.K;
+  const bool pv = f.prev.bn.mean != nullptr;
+  const bool al16 = ((uintptr_t)f.x & 15) == 0 && ((uintptr_t)f.G & 15) == 0;
+  const int64_t rows = (int64_t)f.N * C * T;
+  if (pv && (K != 1 || !gather_prev_supported(C, T, V) || !al16))
     return hipErrorInvalidValue;  // (x from U: k_gather4 only; checked by the caller first)
-  if (!pv && !amax && K > 1 && (V == 25 || V == 50) && ((uintptr_t)x & 15) == 0 &&
-      ((uintptr_t)G & 15) == 0) {  // partitioned graphs: contraction on MFMA
-    const int64_t rows = (int64_t)N * C * T;
-    const bool done =
-        V == 25 ? (launch_gather_mfma<25, 2>(x, mean, invstd, g, b, A, G, C, T, K, rows, relu, s) ||
-                   launch_gather_mfma<25, 3>(x, mean, invstd, g, b, A, G, C, T, K, rows, relu, s))
-                : (launch_gather_mfma<50, 2>(x, mean, invstd, g, b, A, G, C, T, K, rows, relu, s) ||
-                   launch_gather_mfma<50, 3>(x, mean, invstd, g, b, A, G, C, T, K, rows, relu, s));
-    if (done) return hipGetLastError();
-  }
+  // partitioned graphs: contraction on MFMA
+  if (!pv && !f.amax && K > 1 && (V == 25 || V == 50) && al16 &&
+      (V == 25 ? launch_gather_mfma<25>(f, rows, s) : launch_gather_mfma<50>(f, rows, s)))
+    return hipGetLastError();
   const size_t lds4 = sizeof(float) * ((size_t)2 * 256 * V + (size_t)K * V * ((V + 3) & ~3));
-  if (joint_fast(V) && ((int64_t)C * T) % 256 == 0 && ((uintptr_t)x & 15) == 0 &&
-      ((uintptr_t)G & 15) == 0 && lds4 <= 160 * 1024) {
-    const int64_t rows = (int64_t)N * C * T;
-    const dim3 grid4((unsigned)(rows / 256));
-    if (V == 18)
-      hipLaunchKernelGGL(k_gather4<18>, grid4, dim3(256), lds4, s, x, mean, invstd, g, b, A, G, C, T, K, rows, relu, amax, pvb);
-    else if (V == 25)
-      hipLaunchKernelGGL(k_gather4<25>, grid4, dim3(256), lds4, s, x, mean, invstd, g, b, A, G, C, T, K, rows, relu, amax, pvb);
-    else
-      hipLaunchKernelGGL(k_gather4<50>, grid4, dim3(256), lds4, s, x, mean, invstd, g, b, A, G, C, T, K, rows, relu, amax, pvb);
+  if (joint_fast(V) && ((int64_t)C * T) % 256 == 0 && al16 && lds4 <= 160 * 1024) {
+    dispatch_v(V, [&](auto v) {
+      hipLaunchKernelGGL(k_gather4<decltype(v)::value>, dim3((unsigned)(rows / 256)), dim3(256),
+                         lds4, s, f.x, f.bn.mean, f.bn.invstd, f.bn.g, f.bn.b, f.A, f.G, C, T, K,
+                         rows, f.relu, f.amax, f.prev);
+    });
     return hipGetLastError();
   }
   if (joint_fast(V)) {
-    const int VP = (V + 3) & ~3;
-    const int64_t rows = (int64_t)N * C * T;
-    const size_t lds3 = sizeof(float) * (size_t)K * V * VP;
-    const dim3 grid3((unsigned)((rows + 255) / 256));
-    if (V == 18)
-      hipLaunchKernelGGL(k_gather3<18>, grid3, dim3(256), lds3, s, x, mean, invstd, g, b, A, G, C, T, K, rows, relu, amax);
-    else if (V == 25)
-      hipLaunchKernelGGL(k_gather3<25>, grid3, dim3(256), lds3, s, x, mean, invstd, g, b, A, G, C, T, K, rows, relu, amax);
-    else
-      hipLaunchKernelGGL(k_gather3<50>, grid3, dim3(256), lds3, s, x, mean, invstd, g, b, A, G, C, T, K, rows, relu, amax);
+    const size_t lds3 = sizeof(float) * (size_t)K * V * ((V + 3) & ~3);
+    dispatch_v(V, [&](auto v) {
+      hipLaunchKernelGGL(k_gather3<decltype(v)::value>, dim3((unsigned)((rows + 255) / 256)),
+                         dim3(256), lds3, s, f.x, f.bn.mean, f.bn.invstd, f.bn.g, f.bn.b, f.A, f.G,
+                         C, T, K, rows, f.relu, f.amax);
+    });
     return hipGetLastError();
   }
   const size_t lds = sizeof(float) * ((size_t)K * V * V + kGatherTC * V);
-  hipLaunchKernelGGL(k_gather_fwd, dim3((T + kGatherTC - 1) / kGatherTC, N), dim3(256), lds, s, x,
-                     mean, invstd, g, b, A, G, C, T, V, K, relu, amax);
+  hipLaunchKernelGGL(k_gather_fwd, dim3((T + kGatherTC - 1) / kGatherTC, f.N), dim3(256), lds, s,
+                     f.x, f.bn.mean, f.bn.invstd, f.bn.g, f.bn.b, f.A, f.G, C, T, V, K, f.relu,
+                     f.amax);
   return hipGetLastError();
 }
 
@@ -1390,69 +1374,49 @@ __global__ __launch_bounds__(256) void k_spatial_dx(const float *H, const float 
   for (int e = tid; e < KVV; e += 256) atomicAdd(dA + e, dAs[e]);
 }
 
-// the bwd5 / bwd6 launch (or, dry, whether one of them takes this shape)
-static bool launch_bwd56(const float *H, const float *x, const float *mean, const float *invstd,
-                         const float *g, const float *b, const float *A, float *dx, float *dA,
-                         double *sd, double *sdn, int N, int C, int T, int V, int K, int write_dx,
-                         int relu, bool bf6, hipStream_t s, const PrevBn &prev, bool dry,
-                         float *dA_part = nullptr, int64_t part_cap = 0,
-                         int64_t *nparts = nullptr) {
-  const bool aligned = ((int64_t)N * C * T * V) % 4 == 0 && ((uintptr_t)x & 15) == 0 &&
-                       ((uintptr_t)H & 15) == 0 && ((uintptr_t)dx & 15) == 0;
-  if (aligned && K <= 3 && K * ((V + 1) / 2) * ((V + 31) / 32) <= 48) {
-    const int64_t rows = (int64_t)N * C * T;
-    bool done = false;
-#define STGCN_BWD5(VV, RR, KK)                                                              \
-  launch_bwd5<VV, RR, KK>(H, x, mean, invstd, g, b, A, dx, dA, sd, sdn, C, T, K, rows, write_dx, \
-                          relu, s, prev, dry, dA_part, part_cap, nparts)
-    // partitions K: 1 (uniform), 2 (distance), 3 (spatial) labelling
-    if (V == 18)
-      done = STGCN_BWD5(18, 128, 1) || STGCN_BWD5(18, 64, 1) || STGCN_BWD5(18, 128, 2) ||
-             STGCN_BWD5(18, 64, 2) || STGCN_BWD5(18, 128, 3) || STGCN_BWD5(18, 64, 3);
-    else if (V == 25)
-      done = STGCN_BWD5(25, 128, 1) || STGCN_BWD5(25, 64, 1) || STGCN_BWD5(25, 128, 2) ||
-             STGCN_BWD5(25, 64, 2) || STGCN_BWD5(25, 128, 3) || STGCN_BWD5(25, 64, 3);
-    // (V = 50: K * 25 * 2 > 48 for every K, so the guard above sends it to bwd6)
-#undef STGCN_BWD5
-    if (done) return true;
-  }
-  if (aligned && V == 50 && K <= 3) {  // two-person graph, 2 or 3 partitions
-    const int64_t rows = (int64_t)N * C * T;
-    bool done = false;
-#define STGCN_BWD6(KK, BF)                                                                     \
-  launch_bwd6<50, KK, BF>(H, x, mean, invstd, g, b, A, dx, dA, sd, sdn, C, T, K, rows, write_dx, \
-                          relu, s, prev, dry, dA_part, part_cap, nparts)
-    if (bf6)
-      done = STGCN_BWD6(1, true) || STGCN_BWD6(2, true) || STGCN_BWD6(3, true);
-    else
-      done = STGCN_BWD6(1, false) || STGCN_BWD6(2, false) || STGCN_BWD6(3, false);
-#undef STGCN_BWD6
-    if (done) return true;
-  }
+// the six k_spatial_bwd5 forms of a joint count: rows per block, partitions K
+// (1 uniform, 2 distance, 3 spatial labelling)
+template <int V>
+static bool launch_bwd5_v(const SpatialBwd &b, int64_t rows, bool dry, hipStream_t s) {
+  return launch_bwd5<V, 128, 1>(b, rows, dry, s) || launch_bwd5<V, 64, 1>(b, rows, dry, s) ||
+         launch_bwd5<V, 128, 2>(b, rows, dry, s) || launch_bwd5<V, 64, 2>(b, rows, dry, s) ||
+         launch_bwd5<V, 128, 3>(b, rows, dry, s) || launch_bwd5<V, 64, 3>(b, rows, dry, s);
+}
+template <bool BF>
+static bool launch_bwd6_k(const SpatialBwd &b, int64_t rows, bool dry, hipStream_t s) {
+  return launch_bwd6<50, 1, BF>(b, rows, dry, s) || launch_bwd6<50, 2, BF>(b, rows, dry, s) ||
+         launch_bwd6<50, 3, BF>(b, rows, dry, s);
+}
+
+// the bwd5 / bwd6 launch; dry: only whether one of them takes this shape, given
+// 16-byte aligned tensors (no pointer of b is read)
+static bool launch_bwd56(const SpatialBwd &b, bool dry, hipStream_t s) {
+  const int V = b.V, K = b.K;
+  const int64_t rows = (int64_t)b.N * b.C * b.T;
+  const bool aligned = (rows * V) % 4 == 0 &&
+                       (dry || (((uintptr_t)b.x & 15) == 0 && ((uintptr_t)b.in & 15) == 0 &&
+                                ((uintptr_t)b.dx & 15) == 0));
+  if (!aligned || K > 3) return false;
+  // (V = 50: K * 25 * 2 > 48 for every K, so it goes to bwd6)
+  if ((V == 18 || V == 25) && K * ((V + 1) / 2) * ((V + 31) / 32) <= 48)
+    return V == 18 ? launch_bwd5_v<18>(b, rows, dry, s) : launch_bwd5_v<25>(b, rows, dry, s);
+  // two-person graph (bf16 blocks: the two-plane k_spatial_bwd6, fp32 paths: its exact-split form)
+  if (V == 50)
+    return b.bf16ops ? launch_bwd6_k<true>(b, rows, dry, s) : launch_bwd6_k<false>(b, rows, dry, s);
   return false;
 }
 
 bool spatial_dx_prev_supported(int N, int C, int T, int V, int K) {
-  // (16-byte aligned operands: any non-null aligned stand-in pointer)
-  const float *p = reinterpret_cast<const float *>(uintptr_t(256));
-  return launch_bwd56(p, p, nullptr, nullptr, nullptr, nullptr, nullptr, const_cast<float *>(p),
-                      nullptr, nullptr, nullptr, N, C, T, V, K, 1, 0, true, nullptr, PrevBn(), true);
+  SpatialBwd b;
+  b.N = N, b.C = C, b.T = T, b.V = V, b.K = K;
+  return launch_bwd56(b, true, nullptr);
 }
 
-hipError_t launch_spatial_dx(const float *H, const float *x, const float *mean,
-                             const float *invstd, const float *g, const float *b, const float *A,
-                             float *dx, float *dA, double *sd, double *sdn, int N, int C, int T,
-                             int V, int K, int write_dx, int relu, int bf16ops, hipStream_t s,
-                             const PrevBn *prev, float *dA_part, int64_t part_cap,
-                             int64_t *nparts) {
-  if (nparts) *nparts = 0;
-  // (V = 50: bf16 blocks run the two-plane k_spatial_bwd6, the fp32 paths its exact-split form)
-  const bool bf6 = bf16ops != 0;
-  const PrevBn pv = prev ? *prev : PrevBn();
-  if (launch_bwd56(H, x, mean, invstd, g, b, A, dx, dA, sd, sdn, N, C, T, V, K, write_dx, relu,
-                   bf6, s, pv, false, dA_part, part_cap, nparts))
-    return hipGetLastError();
-  if (pv.mean) return hipErrorInvalidValue;  // (callers check spatial_dx_prev_supported)
+hipError_t launch_spatial_dx(const SpatialBwd &b, hipStream_t s) {
+  const int N = b.N, C = b.C, T = b.T, V = b.V, K = b.K;
+  if (b.nparts) *b.nparts = 0;
+  if (launch_bwd56(b, false, s)) return hipGetLastError();
+  if (b.prev.bn.mean) return hipErrorInvalidValue;  // (callers check spatial_dx_prev_supported)
   if (joint_fast(V) && K <= 3) {
     const int VP = (V + 3) & ~3;
     const int RB = bwd3_rows(V, K);
@@ -1462,23 +1426,20 @@ hipError_t launch_spatial_dx(const float *H, const float *x, const float *mean,
                                          (size_t)(RB / 64) * K * DW3 * DW3);
     const dim3 grid3((unsigned)((rows + RB - 1) / RB));
     // (per-workgroup dA partials where the caller's buffer holds them all)
-    float *part = dA_part && (int64_t)grid3.x <= part_cap ? dA_part : nullptr;
-    if (part && nparts) *nparts = grid3.x;
-    if (V == 18)
-      hipLaunchKernelGGL(k_spatial_bwd3<18>, grid3, dim3(RB), lds3, s, H, x, mean, invstd, g, b, A,
-                         dx, dA, sd, sdn, C, T, K, rows, write_dx, relu, part);
-    else if (V == 25)
-      hipLaunchKernelGGL(k_spatial_bwd3<25>, grid3, dim3(RB), lds3, s, H, x, mean, invstd, g, b, A,
-                         dx, dA, sd, sdn, C, T, K, rows, write_dx, relu, part);
-    else
-      hipLaunchKernelGGL(k_spatial_bwd3<50>, grid3, dim3(RB), lds3, s, H, x, mean, invstd, g, b, A,
-                         dx, dA, sd, sdn, C, T, K, rows, write_dx, relu, part);
+    float *part = b.dA_part && (int64_t)grid3.x <= b.part_cap ? b.dA_part : nullptr;
+    if (part && b.nparts) *b.nparts = grid3.x;
+    dispatch_v(V, [&](auto v) {
+      hipLaunchKernelGGL(k_spatial_bwd3<decltype(v)::value>, grid3, dim3(RB), lds3, s, b.in, b.x,
+                         b.bn.mean, b.bn.invstd, b.bn.g, b.bn.b, b.A, b.dx, b.dA, b.sd, b.sdn, C, T,
+                         K, rows, b.write_dx, b.relu, part);
+    });
     return hipGetLastError();
   }
   if (K * V * V > 8192) return hipErrorInvalidValue;
   const size_t lds = sizeof(float) * (2 * (size_t)K * V * V + kDxTC * V + (size_t)K * kDxTC * V);
-  hipLaunchKernelGGL(k_spatial_dx, dim3((T + kDxTC - 1) / kDxTC, N), dim3(256), lds, s, H, x,
-                     mean, invstd, g, b, A, dx, dA, sd, sdn, C, T, V, K, write_dx, relu);
+  hipLaunchKernelGGL(k_spatial_dx, dim3((T + kDxTC - 1) / kDxTC, N), dim3(256), lds, s, b.in, b.x,
+                     b.bn.mean, b.bn.invstd, b.bn.g, b.bn.b, b.A, b.dx, b.dA, b.sd, b.sdn, C, T, V,
+                     K, b.write_dx, b.relu);
   return hipGetLastError();
 }
 

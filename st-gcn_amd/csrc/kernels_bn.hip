@@ -271,18 +271,17 @@ __global__ __launch_bounds__(256) void k_bn_relu_stats(const float *U, const flo
   bn_relu_fwd_body<VEC, false>(U, mean, invstd, g, b, y, N, C, L, ysum, ysq, drop, yext, ymax);
 }
 
-hipError_t launch_bn_relu_fwd(const float *U, const float *mean, const float *invstd,
-                              const float *g, const float *b, float *y, int N, int C, int L,
+hipError_t launch_bn_relu_fwd(const float *U, const BnRef &bn, float *y, int N, int C, int L,
                               double *ysum, double *ysq, Dropout drop, hipStream_t s,
                               double *yext, unsigned *ymax) {
   if (!y) {
     if (!ysum) return hipErrorInvalidValue;  // (nothing to form)
     STGCN_VEC_LAUNCH(k_bn_relu_stats, slice_vec(L, {U}), dim3(C, (N + kBnRows - 1) / kBnRows), U,
-                     mean, invstd, g, b, y, N, C, L, ysum, ysq, drop, yext, ymax);
+                     bn.mean, bn.invstd, bn.g, bn.b, y, N, C, L, ysum, ysq, drop, yext, ymax);
     return hipGetLastError();
   }
   STGCN_VEC_LAUNCH(k_bn_relu_fwd, slice_vec(L, {U, y}), dim3(C, (N + kBnRows - 1) / kBnRows), U,
-                   mean, invstd, g, b, y, N, C, L, ysum, ysq, drop, yext, ymax);
+                   bn.mean, bn.invstd, bn.g, bn.b, y, N, C, L, ysum, ysq, drop, yext, ymax);
   return hipGetLastError();
 }
 
@@ -324,12 +323,9 @@ __global__ __launch_bounds__(256) void k_bn_relu_bwd_reduce(const float *dy, con
   block_sum2_atomic<256>(s, q, sg + c, sgu + c, red);
 }
 
-hipError_t launch_bn_relu_bwd_reduce(const float *dy, const float *U, const float *mean,
-                                     const float *invstd, const float *g, const float *b, int N,
-                                     int C, int L, double *sg, double *sgu, Dropout drop,
-                                     hipStream_t s, const float *dync) {
-  STGCN_VEC_LAUNCH(k_bn_relu_bwd_reduce, slice_vec(L, {dy, U}), dim3(C, N), dy, U, mean, invstd,
-                   g, b, C, L, sg, sgu, drop, dync);
+hipError_t launch_bn_relu_bwd_reduce(const Bn2Bwd &q, double *sg, double *sgu, hipStream_t s) {
+  STGCN_VEC_LAUNCH(k_bn_relu_bwd_reduce, slice_vec(q.L, {q.dy, q.U}), dim3(q.C, q.N), q.dy, q.U,
+                   q.bn.mean, q.bn.invstd, q.bn.g, q.bn.b, q.C, q.L, sg, sgu, q.drop, q.dy_nc);
   return hipGetLastError();
 }
 
@@ -397,16 +393,13 @@ __global__ __launch_bounds__(256) void k_bn_relu_bwd_apply(
   block_sum2_atomic<256>(s, 0.0, sdu + c, nullptr, red);
 }
 
-hipError_t launch_bn_relu_bwd_apply(const float *dy, const float *U, const float *mean,
-                                    const float *invstd, const float *g, const float *b,
-                                    const double *sg, const double *sgu, float *dU, double *sdu,
-                                    int N, int C, int L, int training, Dropout drop,
-                                    hipStream_t s, int du_bf16, const float *dy_coef,
-                                    const float *dync) {
-  // eval mode (constant running statistics): no batch-mean terms
-  const double invM = training ? 1.0 / ((double)N * L) : 0.0;
-  STGCN_VEC_LAUNCH(k_bn_relu_bwd_apply, slice_vec(L, {dy, U, dU}), dim3(C, N), dy, U, mean,
-                   invstd, g, b, sg, sgu, dU, sdu, C, L, invM, drop, du_bf16, dy_coef, dync);
+// 1 / M of the apply passes (eval mode, constant running statistics: no batch-mean terms)
+static double bn2_inv_m(const Bn2Bwd &q) { return q.training ? 1.0 / ((double)q.N * q.L) : 0.0; }
+
+hipError_t launch_bn_relu_bwd_apply(const Bn2Bwd &q, hipStream_t s) {
+  STGCN_VEC_LAUNCH(k_bn_relu_bwd_apply, slice_vec(q.L, {q.dy, q.U, q.dU}), dim3(q.C, q.N), q.dy,
+                   q.U, q.bn.mean, q.bn.invstd, q.bn.g, q.bn.b, q.sg, q.sgu, q.dU, q.sdu, q.C, q.L,
+                   bn2_inv_m(q), q.drop, q.du_bf16, q.dy_coef, q.dy_nc);
   return hipGetLastError();
 }
 
@@ -614,37 +607,26 @@ __global__ __launch_bounds__(256) void k_bn_relu_bwd_apply_fr(
   block_sum2_atomic<256>(s, 0.0, sdu + c, nullptr, red);
 }
 
-hipError_t launch_bn_relu_bwd_apply_fr(const float *dy, const float *U, const float *mean,
-                                       const float *invstd, const float *g, const float *b,
-                                       const double *sg, const double *sgu, float *dU, float *dUA,
-                                       double *sdu, int N, int C, int To, int V, int training,
-                                       Dropout drop, const float *dy_coef, double *cs,
-                                       unsigned *amax, unsigned *amaxa, const float *A,
-                                       hipStream_t s) {
-  if (V != 18 || !amax || !amaxa || !A) return hipErrorInvalidValue;
-  const double invM = training ? 1.0 / ((double)N * To * V) : 0.0;
+hipError_t launch_bn_relu_bwd_apply_fr(const Bn2Bwd &q, hipStream_t s) {
+  if (q.V != 18 || !q.amax || !q.amaxa || !q.A) return hipErrorInvalidValue;
+  const int To = q.L / q.V;
   hipLaunchKernelGGL((k_bn_relu_bwd_apply_fr<18>),
-                     dim3(C, (To + kFrTile - 1) / kFrTile, apply_cols_chunks(N)), dim3(256), 0, s,
-                     dy, U, mean, invstd, g, b, sg, sgu, dU, dUA, sdu, N, C, To, invM, drop, dy_coef,
-                     cs, amax, amaxa, A);
+                     dim3(q.C, (To + kFrTile - 1) / kFrTile, apply_cols_chunks(q.N)), dim3(256), 0,
+                     s, q.dy, q.U, q.bn.mean, q.bn.invstd, q.bn.g, q.bn.b, q.sg, q.sgu, q.dU, q.dUA,
+                     q.sdu, q.N, q.C, To, bn2_inv_m(q), q.drop, q.dy_coef, q.cs, q.amax, q.amaxa,
+                     q.A);
   return hipGetLastError();
 }
 
-hipError_t launch_bn_relu_bwd_apply_cols(const float *dy, const float *U, const float *mean,
-                                         const float *invstd, const float *g, const float *b,
-                                         const double *sg, const double *sgu, float *dU,
-                                         double *sdu, int N, int C, int L, int training,
-                                         Dropout drop, hipStream_t s, int du_bf16,
-                                         const float *dy_coef, double *cs, unsigned *amax,
-                                         const float *dync) {
-  const double invM = training ? 1.0 / ((double)N * L) : 0.0;
+hipError_t launch_bn_relu_bwd_apply_cols(const Bn2Bwd &q, hipStream_t s) {
   // (whole-row vectors: every row start VEC-aligned needs L % VEC == 0)
-  int vec = slice_vec(L, {dy, U, dU});
-  const int nz = apply_cols_chunks(N);
-#define COLS_LAUNCH(VV)                                                                     \
-  hipLaunchKernelGGL((k_bn_relu_bwd_apply_cols<VV>), dim3(C, (L + 256 * VV - 1) / (256 * VV), nz), \
-                     dim3(256), 0, s, dy, U, mean, invstd, g, b, sg, sgu, dU, sdu, N, C, L,  \
-                     invM, drop, du_bf16, dy_coef, cs, amax, dync)
+  int vec = slice_vec(q.L, {q.dy, q.U, q.dU});
+  const int nz = apply_cols_chunks(q.N);
+#define COLS_LAUNCH(VV)                                                                        \
+  hipLaunchKernelGGL((k_bn_relu_bwd_apply_cols<VV>),                                           \
+                     dim3(q.C, (q.L + 256 * VV - 1) / (256 * VV), nz), dim3(256), 0, s, q.dy,  \
+                     q.U, q.bn.mean, q.bn.invstd, q.bn.g, q.bn.b, q.sg, q.sgu, q.dU, q.sdu, q.N, \
+                     q.C, q.L, bn2_inv_m(q), q.drop, q.du_bf16, q.dy_coef, q.cs, q.amax, q.dy_nc)
   if (vec == 4)
     COLS_LAUNCH(4);
   else if (vec == 2)
@@ -685,12 +667,12 @@ __global__ void k_chain_coef(const double *sd, const double *sdn, const float *m
   psum[C + c] = a * (s2[c] - md * su - mdn * is * (xu - mu * su));
 }
 
-hipError_t launch_chain_coef(const double *sd, const double *sdn, const float *mean1,
-                             const float *invstd1, const float *g1, const double *s1,
-                             const double *s2, const double *xst, int C, int64_t M,
-                             float *dg1, float *db1, float *coef, double *psum, hipStream_t s) {
-  hipLaunchKernelGGL(k_chain_coef, dim3((C + 255) / 256), dim3(256), 0, s, sd, sdn, mean1,
-                     invstd1, g1, s1, s2, xst, C, 1.0 / (double)M, dg1, db1, coef, psum);
+hipError_t launch_chain_coef(const double *sd, const double *sdn, const BnRef &bn1,
+                             const double *s1, const double *s2, const double *xst, int C,
+                             int64_t M, float *dg1, float *db1, float *coef, double *psum,
+                             hipStream_t s) {
+  hipLaunchKernelGGL(k_chain_coef, dim3((C + 255) / 256), dim3(256), 0, s, sd, sdn, bn1.mean,
+                     bn1.invstd, bn1.g, s1, s2, xst, C, 1.0 / (double)M, dg1, db1, coef, psum);
   return hipGetLastError();
 }
 
@@ -775,15 +757,13 @@ __global__ __launch_bounds__(256) void k_bn1_bwd_apply(float *dx, const float *x
   if (pg2) block_sum2_atomic<256>(s, q, psum + c, psum + C + c, red);
 }
 
-hipError_t launch_bn1_bwd_apply(float *dx, const float *x, const float *mean, const float *invstd,
-                                const float *g, const double *sd, const double *sdn,
-                                const float *add, int N, int C, int L, int64_t M, int training,
-                                const float *pg2, const float *pb2, double *psum,
-                                const float *pU, const float *pmean, const float *pinvstd,
-                                hipStream_t s) {
-  STGCN_VEC_LAUNCH(k_bn1_bwd_apply, slice_vec(L, {dx, x, add, pU}), dim3(C, N), dx, x, mean,
-                   invstd, g, sd, sdn, add, C, L, training ? 1.0 / (double)M : 0.0, pg2, pb2,
-                   psum, pU, pmean, pinvstd);
+hipError_t launch_bn1_bwd_apply(float *dx, const float *x, const BnRef &bn1, const double *sd,
+                                const double *sdn, const float *add, int N, int C, int L,
+                                int64_t M, int training, const BnRef &pbn2, double *psum,
+                                const float *pU, hipStream_t s) {
+  STGCN_VEC_LAUNCH(k_bn1_bwd_apply, slice_vec(L, {dx, x, add, pU}), dim3(C, N), dx, x, bn1.mean,
+                   bn1.invstd, bn1.g, sd, sdn, add, C, L, training ? 1.0 / (double)M : 0.0, pbn2.g,
+                   pbn2.b, psum, pU, pbn2.mean, pbn2.invstd);
   return hipGetLastError();
 }
 

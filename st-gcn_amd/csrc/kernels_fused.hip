@@ -77,11 +77,13 @@ struct SpFwdGeo : SpFwdGeoBase<V, K, 256, 64> {
 };
 
 struct SpFwdParams {
-  const float *x, *mean, *invstd, *g, *b, *A;
-  // ABI 8 (STGCN_PLAN_X_FROM_U; pmean non-null): x holds the previous block's U
+  const float *x;
+  BnRef bn;
+  const float *A;
+  // ABI 8 (STGCN_PLAN_X_FROM_U; pbn.mean non-null): x holds the previous block's U
   // and the input is ReLU(BN2_prev(U)), formed on staging as k_bn_relu_fwd forms
   // its y (the previous block then writes only y's statistics)
-  const float *pmean, *pinvstd, *pg, *pb;
+  BnRef pbn;
   const __bf16 *aimg;  // the LDS image of the A planes (k_pack_sp_a), DMA'd per workgroup
   const __bf16 *wpk;  // [rt][chunk][k][octet][64][8]
   __bf16 *Gk;         // optional kept G (bf16 tile layout), or null
@@ -98,13 +100,13 @@ __device__ __forceinline__ void spf_bn_table(const SpFwdParams &P, float *bnt, i
     const int c = chunk * G::CK + tid;
     float mu = 0.f, a = 0.f, be = 0.f, pmu = 0.f, pa = 0.f, pbe = 0.f;
     if (c < P.C) {
-      mu = P.mean[c];
-      a = P.invstd[c] * P.g[c];
-      be = P.b[c];
-      if (P.pmean) {
-        pmu = P.pmean[c];
-        pa = P.pinvstd[c] * P.pg[c];
-        pbe = P.pb[c];
+      mu = P.bn.mean[c];
+      a = P.bn.invstd[c] * P.bn.g[c];
+      be = P.bn.b[c];
+      if (P.pbn.mean) {
+        pmu = P.pbn.mean[c];
+        pa = P.pbn.invstd[c] * P.pbn.g[c];
+        pbe = P.pbn.b[c];
       }
     }
     float *tb = bnt + slot * 96;
@@ -194,7 +196,7 @@ __global__ __launch_bounds__(256, 2) void k_sp_fwd_bf16(SpFwdParams P) {
         float v = 0.f;
         if (chunk * G::CK + ch < P.C && goff[k] != kOOB) {
           float xx = st[k];
-          if (P.pmean) {
+          if (P.pbn.mean) {
             const float u = (xx - tb[48 + ch]) * tb[64 + ch] + tb[80 + ch];
             xx = u > 0.f ? u : 0.f;
           }
@@ -441,7 +443,7 @@ __global__ __launch_bounds__(512, 1) void k_sp_fwd_wide(SpFwdParams P) {
         float v = 0.f;
         if (chunk * G::CK + ch < P.C && pos < pos_lim) {
           float xx = st[k];
-          if (P.pmean) {
+          if (P.pbn.mean) {
             const float u = (xx - tb[48 + ch]) * tb[64 + ch] + tb[80 + ch];
             xx = u > 0.f ? u : 0.f;
           }
@@ -722,12 +724,8 @@ static void launch_spw(const SpFwdParams &P, int nblk, hipStream_t s) {
   hipLaunchKernelGGL((k_sp_fwd_wide<V, K, ROWS>), dim3(nblk), dim3(512), lds, s, P);
 }
 
-hipError_t launch_sp_fwd_bf16(const float *x, const float *mean, const float *invstd,
-                              const float *g, const float *b, const float *A, const float *W,
-                              const float *biasZ, void *wpk, float *Z, int z_bf16, __bf16 *Gk,
-                              double *ssum,
-                              double *ssq, int N, int C, int R, int T, int V, int K, int relu,
-                              hipStream_t s, const PrevBn *prev) {
+hipError_t launch_sp_fwd_bf16(const SpatialFwd &f, hipStream_t s) {
+  const int N = f.N, C = f.C, R = f.R, T = f.T, V = f.V, K = f.K, relu = f.relu;
   if (!sp_fwd_bf16_supported(C, V, K, R, relu != 0)) return hipErrorInvalidValue;
   // all output channels per workgroup: the two-person graph, and V = 25 with
   // K = 3 (the 64-row k_sp_fwd_bf16 there measured slower, cfg3 5,301 vs 5,835
@@ -738,45 +736,37 @@ hipError_t launch_sp_fwd_bf16(const float *x, const float *mean, const float *in
   const int nrt = (R + rows - 1) / rows;
   {
     const int64_t total = (int64_t)nrt * nch * K * 2 * rows * 8;
-    hipLaunchKernelGGL(k_pack_sp_w_bf16, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, W,
-                       reinterpret_cast<__bf16 *>(wpk), K, R, C, nch, rows, total);
+    hipLaunchKernelGGL(k_pack_sp_w_bf16, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s,
+                       f.W, reinterpret_cast<__bf16 *>(f.wpk), K, R, C, nch, rows, total);
   }
   // the A image after the packed W' in the scratch
   const size_t wbytes = ((size_t)nrt * nch * K * 2 * rows * 8 * 2 + 1023) & ~(size_t)1023;
-  __bf16 *aimg = reinterpret_cast<__bf16 *>(reinterpret_cast<char *>(wpk) + wbytes);
+  __bf16 *aimg = reinterpret_cast<__bf16 *>(reinterpret_cast<char *>(f.wpk) + wbytes);
   {
     const int KW = (V + 15) & ~15, XP = KW + 8, GC = (K * V + 31) / 32;
     const int plane = GC * 32 * XP;
     const int total = (2 * plane * 2 + 1023) / 1024 * 1024 / 2;  // bf16 elements, whole KiB
-    hipLaunchKernelGGL(k_pack_sp_a, dim3((total + 255) / 256), dim3(256), 0, s, A, aimg, K, V, GC,
+    hipLaunchKernelGGL(k_pack_sp_a, dim3((total + 255) / 256), dim3(256), 0, s, f.A, aimg, K, V, GC,
                        XP, plane, total);
   }
   SpFwdParams P{};
   P.aimg = aimg;
-  P.x = x;
-  P.mean = mean;
-  P.invstd = invstd;
-  P.g = g;
-  P.b = b;
-  P.A = A;
-  if (prev && prev->mean) {
-    P.pmean = prev->mean;
-    P.pinvstd = prev->invstd;
-    P.pg = prev->g;
-    P.pb = prev->b;
-  }
-  P.wpk = reinterpret_cast<const __bf16 *>(wpk);
-  P.Gk = Gk;
+  P.x = f.x;
+  P.bn = f.bn;
+  P.A = f.A;
+  P.pbn = f.prev.bn;
+  P.wpk = reinterpret_cast<const __bf16 *>(f.wpk);
+  P.Gk = f.Gk;
   P.C = C;
   P.T = T;
   P.relu = relu;
   P.nchunks = nch;
   ConvGemmParams &p = P.ep;
-  p.out = Z;
-  p.out_bf16 = z_bf16;
-  p.bias_rv = biasZ;
-  p.stat_sum = ssum;
-  p.stat_sq = ssq;
+  p.out = f.Z;
+  p.out_bf16 = f.z_bf16;
+  p.bias_rv = f.biasZ;
+  p.stat_sum = f.ssum;
+  p.stat_sq = f.ssq;
   p.out_bstride = (int64_t)R * T * V;
   p.R = R;
   p.V = V;
@@ -789,28 +779,22 @@ hipError_t launch_sp_fwd_bf16(const float *x, const float *mean, const float *in
   p.n_mtiles = (T + p.FT - 1) / p.FT;
   p.n_rtiles = nrt;
   const int nblk = N * p.n_mtiles * nrt;
-  if (wide && V == 50) {
-    if (rows == 64) launch_spw<50, 3, 64>(P, nblk, s);
-    else if (rows == 128) launch_spw<50, 3, 128>(P, nblk, s);
-    else launch_spw<50, 3, 256>(P, nblk, s);
-    return hipGetLastError();
-  }
-  if (wide) {
-    if (rows == 64) launch_spw<25, 3, 64>(P, nblk, s);
-    else if (rows == 128) launch_spw<25, 3, 128>(P, nblk, s);
-    else launch_spw<25, 3, 256>(P, nblk, s);
-    return hipGetLastError();
-  }
-#define SPF_K(VV)                            \
-  if (K == 1) launch_spf<VV, 1>(P, nblk, s); \
-  else if (K == 2) launch_spf<VV, 2>(P, nblk, s); \
-  else launch_spf<VV, 3>(P, nblk, s);
-  if (V == 18) {
-    SPF_K(18)
-  } else {
-    SPF_K(25)
-  }
-#undef SPF_K
+  dispatch_v(V, [&](auto v) {
+    constexpr int VV = decltype(v)::value;
+    if constexpr (VV != 18) {
+      if (wide) {
+        if (rows == 64) launch_spw<VV, 3, 64>(P, nblk, s);
+        else if (rows == 128) launch_spw<VV, 3, 128>(P, nblk, s);
+        else launch_spw<VV, 3, 256>(P, nblk, s);
+        return;
+      }
+    }
+    if constexpr (VV != 50) {
+      if (K == 1) launch_spf<VV, 1>(P, nblk, s);
+      else if (K == 2) launch_spf<VV, 2>(P, nblk, s);
+      else launch_spf<VV, 3>(P, nblk, s);
+    }
+  });
   return hipGetLastError();
 }
 

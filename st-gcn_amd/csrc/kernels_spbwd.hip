@@ -94,7 +94,8 @@ struct SpBwdGeo {
 };
 
 struct SpBwdParams {
-  const float *dZ, *x, *mean, *invstd, *g, *b;
+  const float *dZ, *x;
+  BnRef bn;
   const __bf16 *wpk;   // [cb][chunk][k][octet][ci 32][8]
   const __bf16 *aimg;  // [k][ks][plane][lane][8]
   float *dx, *dA;
@@ -121,19 +122,19 @@ __global__ __launch_bounds__(512, 1) void k_sp_bwd_fused(SpBwdParams P) {
   // ---- prologue: BN tables of all channels, zeroed sums and zero row, A image
   float *tab = reinterpret_cast<float *>(lds + G::OFF_TAB);
   double *sums = reinterpret_cast<double *>(lds + G::OFF_SUM);
-  const bool pv = P.prev.mean != nullptr;
+  const bool pv = P.prev.bn.mean != nullptr;
   for (int c = tid; c < P.C; c += 512) {
-    const float is = P.invstd[c];
-    tab[c] = P.mean[c];
+    const float is = P.bn.invstd[c];
+    tab[c] = P.bn.mean[c];
     tab[G::CMAX + c] = is;
-    tab[2 * G::CMAX + c] = is * P.g[c];
-    tab[3 * G::CMAX + c] = P.b[c];
+    tab[2 * G::CMAX + c] = is * P.bn.g[c];
+    tab[3 * G::CMAX + c] = P.bn.b[c];
     if (pv) {
-      const float pis = P.prev.invstd[c];
-      tab[4 * G::CMAX + c] = P.prev.mean[c];
+      const float pis = P.prev.bn.invstd[c];
+      tab[4 * G::CMAX + c] = P.prev.bn.mean[c];
       tab[5 * G::CMAX + c] = pis;
-      tab[6 * G::CMAX + c] = pis * P.prev.g[c];
-      tab[7 * G::CMAX + c] = P.prev.b[c];
+      tab[6 * G::CMAX + c] = pis * P.prev.bn.g[c];
+      tab[7 * G::CMAX + c] = P.prev.bn.b[c];
     }
     sums[c] = 0.0;
     sums[G::CMAX + c] = 0.0;
@@ -526,7 +527,8 @@ struct Sp50Geo {
 };
 
 struct Sp50Params {
-  const float *dZ, *x, *mean, *invstd, *g, *b;
+  const float *dZ, *x;
+  BnRef bn;
   const __bf16 *wpk;   // [cb][chunk][k][octet][ci 32][8]
   const __bf16 *aimg;  // [k][wt][vt][ks][plane][lane][8]
   float *dx, *dA;
@@ -628,12 +630,12 @@ __global__ __launch_bounds__(512, 1) void k_sp50_dx(Sp50Params P) {
   Sp50Ring<K> ring(P, lds0, G::L1_RING, G::L1_W, first, wave, lane, myitems);
   const int NCH = ring.NCH, NG = ring.NG, TV = ring.TV;
   const int nchunks = myitems * NCH;
-  const bool pv = P.prev.mean != nullptr;
+  const bool pv = P.prev.bn.mean != nullptr;
   // this lane's channel (every item of the workgroup is in block first % ncb)
   const int cb = first % P.ncb, c = cb * 32 + lo;
-  const float mu = P.mean[c], is = P.invstd[c], ga = is * P.g[c], be = P.b[c];
-  const float pmu = pv ? P.prev.mean[c] : 0.f, pis = pv ? P.prev.invstd[c] : 1.f;
-  const float pa = pv ? pis * P.prev.g[c] : 1.f, pb = pv ? P.prev.b[c] : 0.f;
+  const float mu = P.bn.mean[c], is = P.bn.invstd[c], ga = is * P.bn.g[c], be = P.bn.b[c];
+  const float pmu = pv ? P.prev.bn.mean[c] : 0.f, pis = pv ? P.prev.bn.invstd[c] : 1.f;
+  const float pa = pv ? pis * P.prev.bn.g[c] : 1.f, pb = pv ? P.prev.bn.b[c] : 0.f;
   {  // A image (48 KiB) by LDS-DMA
     const int4v ra = make_rsrc_words(P.aimg, G::AIMG);
     for (int i = wave; i < G::AIMG / 1024; i += 8)
@@ -838,13 +840,13 @@ __global__ __launch_bounds__(512, 1) void k_sp50_dA(Sp50Params P) {
   Sp50Ring<K> ring(P, lds0, 0, G::L2_W, first, wave, lane, myitems);
   const int NCH = ring.NCH, NG = ring.NG, TV = ring.TV;
   const int nchunks = myitems * NCH;
-  const bool pv = P.prev.mean != nullptr;
+  const bool pv = P.prev.bn.mean != nullptr;
   // row pass thread: channel ci of the block, positions part + 16 q
   const int ci = tid >> 4, part = tid & 15;
   const int cb = first % P.ncb, c = cb * 32 + ci;
-  const float mu = P.mean[c], ga = P.invstd[c] * P.g[c], be = P.b[c];
-  const float pmu = pv ? P.prev.mean[c] : 0.f;
-  const float pa = pv ? P.prev.invstd[c] * P.prev.g[c] : 1.f, pb = pv ? P.prev.b[c] : 0.f;
+  const float mu = P.bn.mean[c], ga = P.bn.invstd[c] * P.bn.g[c], be = P.bn.b[c];
+  const float pmu = pv ? P.prev.bn.mean[c] : 0.f;
+  const float pa = pv ? P.prev.bn.invstd[c] * P.prev.bn.g[c] : 1.f, pb = pv ? P.prev.bn.b[c] : 0.f;
   // zero row of the f(BN1(x)) image (joints past V read it)
   for (int e = tid; e < G::XBP / 4; e += 512)
     reinterpret_cast<unsigned *>(lds + G::L2_XB + G::NPOS * G::XBP)[e] = 0u;
@@ -1048,89 +1050,61 @@ size_t sp_bwd_fused_wpk_bytes(int C, int R, int K, int V) {
   return kSpbAimgBytes + (size_t)K * R * C * 2 * 3 + 256;
 }
 
-template <int V, int K>
-static hipError_t launch_spb(const SpBwdParams &P0, hipStream_t s) {
-  using G = SpBwdGeo<V, K>;
-  SpBwdParams P = P0;
-  P.nft = (P.T + G::FT - 1) / G::FT;
-  const int64_t items = (int64_t)P.ncb * P.nft * P.nitems;  // (nitems: N on entry)
-  if (items >= (int64_t)1 << 31) return hipErrorInvalidValue;
-  P.nitems = (int)items;
-  const int grid = (int)std::min<int64_t>(items, 256);
-  hipLaunchKernelGGL((k_sp_bwd_fused<V, K>), dim3(grid), dim3(512), G::LDS, s, P);
-  return hipGetLastError();
+// SpBwdParams / Sp50Params (the same fields) from the launch descriptor, for
+// tiles of FT frames; nitems < 0: too many work items, the launch is refused
+template <class P>
+static P spb_params(const SpatialBwd &b, const __bf16 *wp, const __bf16 *aimg, int FT) {
+  P p{};
+  p.dZ = b.in;
+  p.x = b.x;
+  p.bn = b.bn;
+  p.wpk = wp;
+  p.aimg = aimg;
+  p.dx = b.dx;
+  p.dA = b.dA;
+  p.sd = b.sd;
+  p.sdn = b.sdn;
+  p.C = b.C;
+  p.R = b.R;
+  p.T = b.T;
+  p.ncb = b.C / 32;
+  p.nft = (b.T + FT - 1) / FT;
+  const int64_t items = (int64_t)p.ncb * p.nft * b.N;
+  p.nitems = items < (int64_t)1 << 31 ? (int)items : -1;
+  p.write_dx = b.write_dx;
+  p.relu = b.relu;
+  p.prev = b.prev;
+  return p;
 }
 
-hipError_t launch_sp_bwd_fused(const float *dZ, const float *x, const float *mean,
-                               const float *invstd, const float *g, const float *b,
-                               const float *A, const float *W, void *wpk, float *dx, float *dA,
-                               double *sd, double *sdn, int N, int C, int R, int T, int V, int K,
-                               int write_dx, int relu, hipStream_t s, const PrevBn *prev,
-                               int only) {
-  if (!sp_bwd_fused_supported(C, V, K, R, T)) return hipErrorInvalidValue;
-  __bf16 *aimg = reinterpret_cast<__bf16 *>(wpk);
+hipError_t launch_sp_bwd_fused(const SpatialBwd &b, hipStream_t s) {
+  if (!sp_bwd_fused_supported(b.C, b.V, b.K, b.R, b.T)) return hipErrorInvalidValue;
+  __bf16 *aimg = reinterpret_cast<__bf16 *>(b.wpk);
   __bf16 *wp = aimg + kSpbAimgBytes / 2;
-  hipLaunchKernelGGL(k_pack_spb_a, dim3(24), dim3(256), 0, s, A, aimg, K, V);
-  const int64_t nw = (int64_t)K * R * C;
+  hipLaunchKernelGGL(k_pack_spb_a, dim3(24), dim3(256), 0, s, b.A, aimg, b.K, b.V);
+  const int64_t nw = (int64_t)b.K * b.R * b.C;
   hipLaunchKernelGGL(k_pack_spb_w, dim3((unsigned)std::min<int64_t>((nw + 255) / 256, 1024)),
-                     dim3(256), 0, s, W, wp, K, R, C);
-  SpBwdParams P{};
-  P.dZ = dZ;
-  P.x = x;
-  P.mean = mean;
-  P.invstd = invstd;
-  P.g = g;
-  P.b = b;
-  P.wpk = wp;
-  P.aimg = aimg;
-  P.dx = dx;
-  P.dA = dA;
-  P.sd = sd;
-  P.sdn = sdn;
-  P.C = C;
-  P.R = R;
-  P.T = T;
-  P.ncb = C / 32;
-  P.nitems = N;
-  P.write_dx = write_dx;
-  P.relu = relu;
-  if (prev) P.prev = *prev;
-  if (V == 50) {  // the two-person graph: k_sp50_dx + k_sp50_dA
+                     dim3(256), 0, s, b.W, wp, b.K, b.R, b.C);
+  if (b.V == 50) {  // the two-person graph: k_sp50_dx + k_sp50_dA
     using G = Sp50Geo<3>;
-    hipLaunchKernelGGL(k_pack_sp50_a, dim3(48), dim3(256), 0, s, A, aimg, K);
-    Sp50Params Q{};
-    Q.dZ = dZ;
-    Q.x = x;
-    Q.mean = mean;
-    Q.invstd = invstd;
-    Q.g = g;
-    Q.b = b;
-    Q.wpk = wp;
-    Q.aimg = aimg;
-    Q.dx = dx;
-    Q.dA = dA;
-    Q.sd = sd;
-    Q.sdn = sdn;
-    Q.C = C;
-    Q.R = R;
-    Q.T = T;
-    Q.ncb = C / 32;
-    Q.nft = (T + G::FT - 1) / G::FT;
-    const int64_t items = (int64_t)Q.ncb * Q.nft * N;
-    if (items >= (int64_t)1 << 31) return hipErrorInvalidValue;
-    Q.nitems = (int)items;
-    Q.write_dx = write_dx && dx != nullptr;
-    Q.relu = relu;
-    if (prev) Q.prev = *prev;
+    hipLaunchKernelGGL(k_pack_sp50_a, dim3(48), dim3(256), 0, s, b.A, aimg, b.K);
+    Sp50Params Q = spb_params<Sp50Params>(b, wp, aimg, G::FT);
+    if (Q.nitems < 0) return hipErrorInvalidValue;
+    Q.write_dx = b.write_dx && b.dx != nullptr;
     // (the grid is a multiple of the channel-block count ncb = C / 32, so every
     // item of a workgroup -- first, first + grid, ... -- is in block first % ncb:
     // 255 at ncb = 3 (C_in = 96); items is itself a multiple of ncb)
-    const int grid = (int)std::min<int64_t>(items, 256 / Q.ncb * Q.ncb);
-    if (only != 2) hipLaunchKernelGGL((k_sp50_dx<3>), dim3(grid), dim3(512), G::LDS1, s, Q);
-    if (only != 1) hipLaunchKernelGGL((k_sp50_dA<3>), dim3(grid), dim3(512), G::LDS2, s, Q);
+    const int grid = std::min(Q.nitems, 256 / Q.ncb * Q.ncb);
+    if (b.only != 2) hipLaunchKernelGGL((k_sp50_dx<3>), dim3(grid), dim3(512), G::LDS1, s, Q);
+    if (b.only != 1) hipLaunchKernelGGL((k_sp50_dA<3>), dim3(grid), dim3(512), G::LDS2, s, Q);
     return hipGetLastError();
   }
-  return launch_spb<25, 3>(P, s);
+  using G = SpBwdGeo<25, 3>;
+  const SpBwdParams P = spb_params<SpBwdParams>(b, wp, aimg, G::FT);
+  if (P.nitems < 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL((k_sp_bwd_fused<25, 3>), dim3(std::min(P.nitems, 256)), dim3(512), G::LDS, s,
+                     P);
+  return hipGetLastError();
 }
 
 }  // namespace stgcn

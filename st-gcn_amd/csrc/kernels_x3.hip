@@ -232,7 +232,7 @@ __device__ __forceinline__ void spb_epilogue(const ConvGemmParams &p, floatx16 (
   const int64_t xbytes = (int64_t)C * cT * 4;
   const int4v rsx = {(int)(uint32_t)xsrc, (int)((xsrc >> 32) & 0xffff),
                      rsrc_size(xbytes), 0x00020000};
-  const bool pv = p.prev.mean != nullptr;
+  const bool pv = p.prev.bn.mean != nullptr;
   const int combo = tid / NSUB, sub = tid - combo * NSUB;
   const int vb = combo / 3, wb = combo - (combo / 3) * 3;
   // The per-row parameters (thread tid < MR * 64: row tid), loaded here, before
@@ -244,9 +244,9 @@ __device__ __forceinline__ void spb_epilogue(const ConvGemmParams &p, floatx16 (
     const int c = r0 + tid;
     const bool rok = tid < MR * 64 && c < C, pok = pv && rok;
     const int cc = rok ? c : 0;  // (a valid address either way)
-    const float *pm = pv ? p.prev.mean : p.mean1, *pi = pv ? p.prev.invstd : p.invstd1;
-    const float *pg = pv ? p.prev.g : p.g1, *pbb = pv ? p.prev.b : p.b1;
-    const float mu = p.mean1[cc], is = p.invstd1[cc], g = p.g1[cc], be = p.b1[cc];
+    const float *pm = pv ? p.prev.bn.mean : p.bn1.mean, *pi = pv ? p.prev.bn.invstd : p.bn1.invstd;
+    const float *pg = pv ? p.prev.bn.g : p.bn1.g, *pbb = pv ? p.prev.bn.b : p.bn1.b;
+    const float mu = p.bn1.mean[cc], is = p.bn1.invstd[cc], g = p.bn1.g[cc], be = p.bn1.b[cc];
     const float qmu = pm[cc], qis = pi[cc], qg = pg[cc], qb = pbb[cc];
     rp[0] = rok ? mu : 0.f;
     rp[1] = rok ? is : 0.f;
@@ -540,9 +540,9 @@ __device__ __forceinline__ float bn1_bound(const ConvGemmParams &p, int c, float
                                            float &a, float &be) {
   mu = a = be = 0.f;
   if (c >= p.C) return 0.f;
-  mu = p.mean1[c];
-  a = p.invstd1[c] * p.g1[c];
-  be = p.b1[c];
+  mu = p.bn1.mean[c];
+  a = p.bn1.invstd[c] * p.bn1.g[c];
+  be = p.bn1.b[c];
   return fabsf(a) * (M + fabsf(mu)) + fabsf(be);
 }
 
@@ -1445,10 +1445,10 @@ hipError_t launch_conv_x3(const ConvGemmParams &p, hipStream_t s) {
   if (!conv_x3_supported(p) || !p.wpk) return hipErrorInvalidValue;
   if (p.f16x2 && (!p.amax_in || !p.amax_w)) return hipErrorInvalidValue;
   if (p.spb && (p.V != 18 || p.s_in != 1 || p.FT != kTileCols / 18 || !p.sx || !p.sA ||
-                !p.mean1 || !p.invstd1 || !p.g1 || !p.b1 || !p.sd || !p.sdn || !p.dA))
+                !p.bn1.mean || !p.bn1.invstd || !p.bn1.g || !p.bn1.b || !p.sd || !p.sdn || !p.dA))
     return hipErrorInvalidValue;
-  if (p.bna && (!p.f16x2 || !conv_x3_bna_supported(p) || !p.sA || !p.mean1 || !p.invstd1 ||
-                !p.g1 || !p.b1))
+  if (p.bna && (!p.f16x2 || !conv_x3_bna_supported(p) || !p.sA || !p.bn1.mean || !p.bn1.invstd ||
+                !p.bn1.g || !p.bn1.b))
     return hipErrorInvalidValue;
   return launch_conv_planes(p, p.f16x2 ? 2 : 3, s);
 }
@@ -1617,16 +1617,16 @@ __global__ __launch_bounds__(512, 1) void k_wgrad_x3(WgradParams p) {
     const float M = __builtin_bit_cast(float, amax_read(p.amax_q));
     float bm = 0.f;
     for (int c = tid; c < p.C; c += 512) {
-      const float a = p.q_invstd[c] * p.q_g[c];
-      bm = fmaxf(bm, fabsf(a) * (M + fabsf(p.q_mean[c])) + fabsf(p.q_b[c]));
+      const float a = p.q_bn.invstd[c] * p.q_bn.g[c];
+      bm = fmaxf(bm, fabsf(a) * (M + fabsf(p.q_bn.mean[c])) + fabsf(p.q_bn.b[c]));
     }
     if (tid <= G::CB) {
       const int c = c0 + tid;
       const bool ok = tid < G::CB && c < p.C;
       *reinterpret_cast<float4 *>(qtab + 4 * tid) =
           tid == G::CB ? make_float4(0.f, 1.f, 0.f, 0.f)
-                       : make_float4(ok ? p.q_mean[c] : 0.f, ok ? p.q_invstd[c] * p.q_g[c] : 0.f,
-                                     ok ? p.q_b[c] : 0.f, 0.f);
+                       : make_float4(ok ? p.q_bn.mean[c] : 0.f, ok ? p.q_bn.invstd[c] * p.q_bn.g[c] : 0.f,
+                                     ok ? p.q_bn.b[c] : 0.f, 0.f);
     }
     q_se = f16x2_se_bits(
         __builtin_bit_cast(unsigned, block_max_all<512>(bm, qtab + 4 * (G::CB + 1))));
@@ -2002,9 +2002,9 @@ bool plan_wgrad_x3(WgradParams &w, bool f16x2) {
 hipError_t launch_wgrad_x3(const WgradParams &p0, hipStream_t s) {
   if (p0.bf16 != 3 || p0.V != 18 || (p0.s_in != 1 && p0.s_in != 2)) return hipErrorInvalidValue;
   const int nblk = p0.n_rtiles * p0.n_jtiles * p0.S;
-  if (p0.f16x2 && p0.q_mean) {  // 2-way fp16 splits, Q = x with BN1 at staging (QBN)
+  if (p0.f16x2 && p0.q_bn.mean) {  // 2-way fp16 splits, Q = x with BN1 at staging (QBN)
     const WgradParams &p = p0;
-    if (!p.amax_p || !p.amax_q || !p.q_invstd || !p.q_g || !p.q_b) return hipErrorInvalidValue;
+    if (!p.amax_p || !p.amax_q || !p.q_bn.invstd || !p.q_bn.g || !p.q_bn.b) return hipErrorInvalidValue;
     if (p.x3_mr == 2 && p.R % 128 != 0) return hipErrorInvalidValue;
     constexpr int ex = (4 * 33 + 8) * 4;  // the Q channel table + block_max_all's scratch
     if (p.s_in == 1 && p.x3_mr == 2)

@@ -349,9 +349,10 @@ struct HeadSrc {
 void launch_pool(const HeadSrc &src, float *pooled, int N, int C, int L, hipStream_t s) {
   const int64_t rows = (int64_t)N * C;
   const dim3 grid((unsigned)((rows + 3) / 4));
+  const stgcn::BnRef bn = stgcn::bn_ref(src.stats2, C, src.g2, src.b2);
   if (src.u)
-    hipLaunchKernelGGL(k_head_pool_u, grid, dim3(256), 0, s, src.x, src.stats2, src.stats2 + C,
-                       src.g2, src.b2, pooled, rows, C, L);
+    hipLaunchKernelGGL(k_head_pool_u, grid, dim3(256), 0, s, src.x, bn.mean, bn.invstd, bn.g, bn.b,
+                       pooled, rows, C, L);
   else
     hipLaunchKernelGGL(k_head_pool, grid, dim3(256), 0, s, src.x, pooled, rows, L);
 }

@@ -39,6 +39,9 @@ CASES = {
     "f32x3_fold_v25": (16, 32, 25, 1, 1, {"f32x3": True}),
     "bf16_v25_k3": (16, 32, 25, 3, 1, {"bf16": True}),
     "bf16_v50_k3": (16, 32, 50, 3, 1, {"bf16": True}),
+    # (C_in a multiple of 32, C_out >= 64: the fused backward pair k_sp50_dx / k_sp50_dA,
+    # which 5 and 6 one of them each)
+    "bf16_v50_k3_fused_bwd": (32, 64, 50, 3, 1, {"bf16": True}),
     "fp32_residual_proj_s2": (16, 32, 18, 1, 2, {"residual": True}),
 }
 
@@ -82,6 +85,8 @@ def test_time_kernel(pkg, name):
         assert plan & hl.PLAN_F16X2 and not plan & hl.PLAN_FOLD
     if name.startswith("bf16"):
         assert plan & hl.PLAN_SP_FWD_FUSED
+    if name == "bf16_v50_k3_fused_bwd":
+        assert plan & hl.PLAN_SP_BWD_FUSED
     ran = 0
     for which in range(7):
         nbytes = lib.stgcn_time_kernel_bytes(ctypes.byref(d), which)
