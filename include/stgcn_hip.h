@@ -58,7 +58,8 @@
  *       STGCN_FEATURE_INPUT_STAGE (stgcn_input_stage): x 16 bytes, like a block
  *         tensor; src its element's own 4 (fp32) or 8 (fp64) bytes; the clip
  *         table 8; status 4. STGCN_FEATURE_INPUT_MOVE (stgcn_input_stage_move): the
- *         same, and the move table 8.
+ *         same, and the move table 8. STGCN_FEATURE_INPUT_STREAMS
+ *         (stgcn_input_stage_streams): the same, and the parents table 4.
  *       STGCN_FEATURE_OPTIMIZERS (stgcn_opt_*): the device table 8; every param /
  *         grad / s0 / s1 / s2 of a table entry, lr_dev, grad_coef and step_dev 4.
  *     A caller with a misaligned read-only input for a 16-byte argument passes an
@@ -320,6 +321,9 @@ const char *stgcn_last_error(void);
                                     * ("random moving") in the input stage              */
 #define STGCN_FEATURE_BWD_OVERLAP 128 /* stgcn_bwd_overlap: the backward's small kernels on an
                                     * internal stream beside its GEMMs                   */
+#define STGCN_FEATURE_INPUT_STREAMS 256 /* stgcn_input_streams_check / stgcn_input_stage_streams:
+                                    * bone, joint-motion and bone-motion streams beside the
+                                    * joints in the input stage                          */
 int stgcn_features(void);
 
 /* STGCN_FEATURE_BWD_OVERLAP: stgcn_block_bwd / _bwd_dseed of a folded block whose
@@ -790,6 +794,54 @@ int stgcn_input_move_check(const stgcn_input_desc_t *d);
 int stgcn_input_stage_move(const stgcn_input_desc_t *d, const void *src,
                            const stgcn_clip_t *clips, const stgcn_move_t *moves, float *x,
                            int32_t *status, void *stream);
+
+/* ---------------------------------------------------------------------------
+ * STGCN_FEATURE_INPUT_STREAMS: the input views the ST-GCN descendants train on
+ * (2s-AGCN, ST-GCN++, the PYSKL recipes), formed by the input stage's launch
+ * from the augmented point, so after the clip's matrix and its move: a bone of
+ * the moved skeleton is not the moved bone of the original.
+ *
+ * x is (N, S * in.C, T_out, V) fp32, written in full; the selected streams come
+ * in bit order (joint, bone, joint motion, bone motion), in.C consecutive
+ * channels each. Let J[c, t, v] be the fp32 value stgcn_input_stage_move writes
+ * for the same src, clips and moves (stgcn_input_stage with moves == NULL): the
+ * kernel forms it with that launch's own operations, so with its bits. With
+ * p = parents[v], in fp32, every operation rounded on its own:
+ *   B [c, t, v] = J[c, t, v] - J[c, t, p]             (p == v, a root: +0)
+ *   JM[c, t, v] = J[c, t + 1, v] - J[c, t, v]         t < T_out - 1, else 0
+ *   BM[c, t, v] = B[c, t + 1, v] - B[c, t, v]         t < T_out - 1, else 0
+ * and on the score channel c == score_channel (a confidence, not a coordinate)
+ * the mean instead of the difference:
+ *   B = (J[c, t, v] + J[c, t, p]) * 0.5f,  JM = (J[c, t + 1, v] + J[c, t, v]) * 0.5f,
+ *   BM = (B[c, t + 1, v] + B[c, t, v]) * 0.5f, the last frame of JM and BM 0 too.
+ * Frame t + 1 is the loop-padded frame first_frame + ((t + 1) mod frames): the
+ * seam of a wrapped clip gives a real difference, as on the padded array.
+ *
+ * parents is a DEVICE table of V int32 entries, read when the kernel runs, like
+ * clips; it may be NULL without a bone bit. An entry outside [0, V) is invalid:
+ * every clip is written as zeros without reading src, and every status[n] has
+ * bit 2 (value 4) set beside the unchanged bits 0 and 1; every launch writes
+ * all N words with plain stores.
+ * stgcn_input_streams_check: STGCN_E_INVALID for an empty mask, unknown bits or
+ * a score_channel other than -1 or in.C - 1 >= 2; STGCN_E_UNSUPPORTED for
+ * V > 256 with a bone bit and for an x of N * S * C * T_out * V elements beyond
+ * the kernel's int64 offsets (the limits of stgcn_input_check hold and are the
+ * tighter ones today). streams ==
+ * STGCN_STREAM_JOINT is the stgcn_input_stage_move launch itself.
+ * Alignment: parents 4 bytes, the rest as stgcn_input_stage_move. */
+#define STGCN_STREAM_JOINT        1
+#define STGCN_STREAM_BONE         2
+#define STGCN_STREAM_JOINT_MOTION 4
+#define STGCN_STREAM_BONE_MOTION  8
+typedef struct stgcn_streams_desc {
+  stgcn_input_desc_t in;   /* as for stgcn_input_stage; in.C channels per stream     */
+  int32_t streams;         /* non-empty subset of the four bits; S = popcount        */
+  int32_t score_channel;   /* -1, or in.C - 1 (>= 2): that channel is a confidence   */
+} stgcn_streams_desc_t;    /* 40 bytes                                               */
+int stgcn_input_streams_check(const stgcn_streams_desc_t *d);
+int stgcn_input_stage_streams(const stgcn_streams_desc_t *d, const void *src,
+                              const stgcn_clip_t *clips, const stgcn_move_t *moves,
+                              const int32_t *parents, float *x, int32_t *status, void *stream);
 
 #ifdef __cplusplus
 }

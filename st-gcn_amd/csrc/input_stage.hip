@@ -19,6 +19,12 @@
 // STGCN_FEATURE_INPUT_MOVE (k_input_stage_move, below): the same launch with one
 // stgcn_move_t per clip -- rotation, scale and translation interpolated over the
 // frames and applied per frame ("random moving"), validated in the kernel too.
+//
+// STGCN_FEATURE_INPUT_STREAMS (k_input_stage_streams): the same launch writing
+// S of the four input streams of the ST-GCN descendants -- joint, bone (joint
+// minus parent joint), joint motion (frame t + 1 minus frame t), bone motion --
+// as S groups of C channels, formed from the augmented point in registers.
+// Algorithmic bytes: N * T_out * V * (C_src * sizeof(src) + 4 * S * C).
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -237,6 +243,194 @@ k_input_stage_move(const S *__restrict__ src, const stgcn_clip_t *__restrict__ c
     if (c < C) out[(int64_t)c * plane] = (float)pt.c[c];
 }
 
+// ---- STGCN_FEATURE_INPUT_STREAMS ---------------------------------------------
+
+// J[.., t, v] of a valid clip from one source point, with the bits of the launch
+// it restates: k_input_stage_move's unfused fp64 sequence on a moved clip (f is
+// the frame's entry of the LDS table), store_point's fused form or plain cast
+// otherwise. moved is uniform per workgroup.
+template <typename S, int CS>
+__device__ __forceinline__ void joint_point(const Point<S, CS> &pt, const stgcn_clip_t &clip,
+                                            bool moved, const Affine &f, float (&j)[CS]) {
+  double px = (double)pt.c[0], py = (double)pt.c[1];
+  if (moved) {
+    if (clip.flags & 1) {
+      const double qx = px * clip.m[0] + py * clip.m[2];
+      py = px * clip.m[1] + py * clip.m[3];
+      px = qx;
+    }
+    j[0] = (float)((f.c * px - f.sn * py) + f.tx);
+    j[1] = (float)((f.sn * px + f.c * py) + f.ty);
+  } else if (clip.flags & 1) {
+    j[0] = (float)__builtin_fma(px, clip.m[0], py * clip.m[2]);
+    j[1] = (float)__builtin_fma(px, clip.m[1], py * clip.m[3]);
+  } else {
+    j[0] = (float)pt.c[0];
+    j[1] = (float)pt.c[1];
+  }
+#pragma unroll
+  for (int c = 2; c < CS; ++c) j[c] = (float)pt.c[c];
+}
+
+// One stream's C plane rows of a point: the difference b - a, or on the score
+// channel the mean (b + a) * 0.5f; fp32, every operation rounded on its own.
+__device__ __forceinline__ float stream_op(float b, float a, bool score) {
+  return score ? (b + a) * 0.5f : b - a;
+}
+
+// The joint, bone, joint-motion and bone-motion streams of the staged input
+// (streams: a non-empty mask of STGCN_STREAM_*, uniform), S = popcount(streams)
+// groups of C channels in bit order: x (N, S * C, T_out, V). Same grid and same
+// point per thread as the kernels above. A thread gathers up to four source
+// points, (t, v), (t, p), (t + 1, v), (t + 1, p) with p = parents[v], forms J
+// at each by joint_point and stores S * C coalesced plane rows; the last frame of
+// the motion streams is 0. Frame t + 1 is the loop-padded one, as for frame t.
+// Algorithmic bytes: N * T_out * V * (C_src * sizeof(src) + 4 * S * C) (the
+// neighbour points are other threads' own points: cache hits).
+// LDS: the parents table (V <= 256 with a bone bit, stgcn_input_streams_check),
+// loaded by the workgroup and validated with one __syncthreads_or, and the
+// frames' affine parameters of a moved clip, now up to frame t + 1: for V = 1
+// the workgroup's 256 points and their successors lie in 257 frames; the general
+// bound 255 / V + 3 gives 258.
+constexpr int kStreamFrames = kMoveFrames + 1;
+constexpr int kMaxParents = 256;  // (the block library's own limit on V)
+constexpr int kAllStreams = STGCN_STREAM_JOINT | STGCN_STREAM_BONE | STGCN_STREAM_JOINT_MOTION |
+                            STGCN_STREAM_BONE_MOTION;
+
+template <typename S, int CS>
+__global__ void __launch_bounds__(kStageThreads)
+k_input_stage_streams(const S *__restrict__ src, const stgcn_clip_t *__restrict__ clips,
+                      const stgcn_move_t *__restrict__ moves,
+                      const int32_t *__restrict__ parents, float *__restrict__ x,
+                      int32_t *__restrict__ status, int C, int T_out, int V, int bpc,
+                      int64_t src_frames, int streams, int score_channel) {
+  __shared__ Affine frames[kStreamFrames];
+  __shared__ int32_t par[kMaxParents];
+  const int n = (int)(blockIdx.x / (unsigned)bpc);
+  const int chunk = (int)(blockIdx.x - (unsigned)n * (unsigned)bpc);
+  const int plane = T_out * V;  // < 2^31 (stgcn_input_check)
+  const int64_t p64 = (int64_t)chunk * kStageThreads + (int64_t)threadIdx.x;
+  const stgcn_clip_t clip = clips[n];
+  const stgcn_move_t *mv = moves ? moves + n : nullptr;  // (fields are loaded where used)
+  const bool clip_ok = clip.frames >= 1 && clip.first_frame >= 0 &&
+                       clip.first_frame <= src_frames - (int64_t)clip.frames;
+  const bool mv_ok = mv ? move_ok(*mv, T_out) : true;
+  const bool bone = (streams & (STGCN_STREAM_BONE | STGCN_STREAM_BONE_MOTION)) != 0;
+  const bool motion = (streams & (STGCN_STREAM_JOINT_MOTION | STGCN_STREAM_BONE_MOTION)) != 0;
+  int par_bad = 0;
+  if (bone) {  // (uniform; V <= kMaxParents) the barrier also publishes par[]
+    int bad = 0;
+    if ((int)threadIdx.x < V) {
+      const int32_t q = parents[threadIdx.x];
+      par[threadIdx.x] = q;
+      bad = q < 0 || q >= V;
+    }
+    par_bad = __syncthreads_or(bad);
+  }
+  if (chunk == 0 && threadIdx.x == 0)
+    status[n] = (clip_ok ? 0 : 1) | (mv_ok ? 0 : 2) | (par_bad ? 4 : 0);
+  const bool live = p64 < plane;
+  const int p = live ? (int)p64 : 0;
+  const int SC = __popc((unsigned)streams) * C;
+  float *out = x + (int64_t)n * SC * plane + p;
+  if (!clip_ok || !mv_ok || par_bad) {  // (uniform)
+    if (live)
+      for (int c = 0; c < SC; ++c) out[(int64_t)c * plane] = 0.f;
+    return;
+  }
+  // the source points first: the loads are in flight while the frames'
+  // parameters are evaluated
+  const int t = p / V, v = p - t * V;
+  const bool next = motion && t + 1 < T_out;  // (the last frame's motion is 0)
+  const int q = bone ? par[v] : v;
+  Point<S, CS> pv = {}, pq = {}, nv = {}, nq = {};
+  if (live) {
+    const int64_t f0 = clip.first_frame + (int64_t)((unsigned)t % (unsigned)clip.frames);
+    pv = *reinterpret_cast<const Point<S, CS> *>(src + (f0 * V + v) * (int64_t)CS);
+    if (bone) pq = *reinterpret_cast<const Point<S, CS> *>(src + (f0 * V + q) * (int64_t)CS);
+    if (next) {
+      const int64_t f1 =
+          clip.first_frame + (int64_t)((unsigned)(t + 1) % (unsigned)clip.frames);
+      nv = *reinterpret_cast<const Point<S, CS> *>(src + (f1 * V + v) * (int64_t)CS);
+      if (bone) nq = *reinterpret_cast<const Point<S, CS> *>(src + (f1 * V + q) * (int64_t)CS);
+    }
+  }
+  const bool moved = mv && mv->nk != 0;  // (uniform)
+  const int t0 = (int)(((int64_t)chunk * kStageThreads) / V);
+  if (moved) {
+    // frames t0 .. t0 + (255 / V + 2), cut at the plane's end: those of the
+    // workgroup's points and of their successors. Every thread of the workgroup
+    // reaches the barrier: the returns above are uniform.
+    const int nf = min((kStageThreads - 1) / V + 3, T_out - t0);
+    for (int i = (int)threadIdx.x; i < nf; i += kStageThreads)
+      frames[i] = frame_affine(*mv, t0 + i);
+    __syncthreads();
+  }
+  if (!live) return;
+  Affine fa = {}, fb = {};
+  if (moved) {
+    fa = frames[t - t0];
+    if (next) fb = frames[t + 1 - t0];
+  }
+  float jv[CS], jq[CS] = {}, kv[CS] = {}, kq[CS] = {};
+  joint_point<S, CS>(pv, clip, moved, fa, jv);
+  if (bone) joint_point<S, CS>(pq, clip, moved, fa, jq);
+  if (next) {
+    joint_point<S, CS>(nv, clip, moved, fb, kv);
+    if (bone) joint_point<S, CS>(nq, clip, moved, fb, kq);
+  }
+  const int64_t group = (int64_t)C * plane;
+  if (streams & STGCN_STREAM_JOINT) {
+#pragma unroll
+    for (int c = 0; c < CS; ++c)
+      if (c < C) out[(int64_t)c * plane] = jv[c];
+    out += group;
+  }
+  if (streams & STGCN_STREAM_BONE) {
+#pragma unroll
+    for (int c = 0; c < CS; ++c)
+      if (c < C) out[(int64_t)c * plane] = stream_op(jv[c], jq[c], c == score_channel);
+    out += group;
+  }
+  if (streams & STGCN_STREAM_JOINT_MOTION) {
+#pragma unroll
+    for (int c = 0; c < CS; ++c)
+      if (c < C)
+        out[(int64_t)c * plane] = next ? stream_op(kv[c], jv[c], c == score_channel) : 0.f;
+    out += group;
+  }
+  if (streams & STGCN_STREAM_BONE_MOTION) {
+#pragma unroll
+    for (int c = 0; c < CS; ++c)
+      if (c < C) {
+        const bool sc = c == score_channel;
+        out[(int64_t)c * plane] =
+            next ? stream_op(stream_op(kv[c], kq[c], sc), stream_op(jv[c], jq[c], sc), sc) : 0.f;
+      }
+  }
+}
+
+template <typename S>
+void launch_streams(const stgcn_streams_desc_t *sd, const void *src, const stgcn_clip_t *clips,
+                    const stgcn_move_t *moves, const int32_t *parents, float *x,
+                    int32_t *status, int bpc, hipStream_t s) {
+  const stgcn_input_desc_t *d = &sd->in;
+  const dim3 grid((unsigned)((int64_t)d->N * bpc)), block(kStageThreads);
+  const S *sp = (const S *)src;
+#define STREAMS_CASE(CS)                                                                        \
+  case CS:                                                                                      \
+    hipLaunchKernelGGL((k_input_stage_streams<S, CS>), grid, block, 0, s, sp, clips, moves,     \
+                       parents, x, status, d->C, d->T_out, d->V, bpc, d->src_frames,            \
+                       sd->streams, sd->score_channel);                                         \
+    break;
+  switch (d->C_src) {
+    STREAMS_CASE(2)
+    STREAMS_CASE(3)
+    STREAMS_CASE(4)
+  }
+#undef STREAMS_CASE
+}
+
 template <typename S>
 void launch_stage(const stgcn_input_desc_t *d, const void *src, const stgcn_clip_t *clips,
                   const stgcn_move_t *moves, float *x, int32_t *status, int bpc, hipStream_t s) {
@@ -268,6 +462,7 @@ int blocks_per_clip(const stgcn_input_desc_t *d) {
 static_assert(sizeof(stgcn_input_desc_t) == 32, "stgcn_input_desc_t is 32 bytes");
 static_assert(sizeof(stgcn_clip_t) == 48, "stgcn_clip_t is 48 bytes");
 static_assert(sizeof(stgcn_move_t) == 160, "stgcn_move_t is 160 bytes");
+static_assert(sizeof(stgcn_streams_desc_t) == 40, "stgcn_streams_desc_t is 40 bytes");
 
 extern "C" {
 
@@ -315,6 +510,56 @@ int stgcn_input_stage_move(const stgcn_input_desc_t *d, const void *src,
   hipError_t e = hipGetLastError();
   if (e != hipSuccess)
     return fail(STGCN_E_HIP, std::string("input_stage launch: ") + hipGetErrorString(e));
+  return STGCN_OK;
+}
+
+int stgcn_input_streams_check(const stgcn_streams_desc_t *d) {
+  if (!d) return fail(STGCN_E_INVALID, "streams: null descriptor");
+  if (int rc = stgcn_input_check(&d->in)) return rc;
+  if (d->streams <= 0 || (d->streams & ~kAllStreams))
+    return fail(STGCN_E_INVALID,
+                "streams: the mask is a non-empty subset of the four STGCN_STREAM_* bits");
+  if (d->score_channel != -1 && (d->score_channel != d->in.C - 1 || d->score_channel < 2))
+    return fail(STGCN_E_INVALID, "streams: score_channel is -1 or in.C - 1 (at least 2)");
+  if ((d->streams & (STGCN_STREAM_BONE | STGCN_STREAM_BONE_MOTION)) && d->in.V > kMaxParents)
+    return fail(STGCN_E_UNSUPPORTED, "streams: a bone stream needs V <= 256");
+  // x (N, S * C, T_out, V) is indexed with int64 element offsets. Today the launch
+  // limit of stgcn_input_check (N * T_out * V < 2^39, and S * C <= 16) keeps it far
+  // inside them; the check stands on its own should that limit ever be relaxed.
+  const int64_t rows = (int64_t)d->in.N * __builtin_popcount((unsigned)d->streams) * d->in.C;
+  if (rows > INT64_MAX / 4 / ((int64_t)d->in.T_out * d->in.V))
+    return fail(STGCN_E_UNSUPPORTED, "streams: N * S * C * T_out * V exceeds the int64 offsets");
+  return STGCN_OK;
+}
+
+int stgcn_input_stage_streams(const stgcn_streams_desc_t *d, const void *src,
+                              const stgcn_clip_t *clips, const stgcn_move_t *moves,
+                              const int32_t *parents, float *x, int32_t *status, void *stream) {
+  if (int rc = stgcn_input_streams_check(d)) return rc;
+  const bool bone = (d->streams & (STGCN_STREAM_BONE | STGCN_STREAM_BONE_MOTION)) != 0;
+  if (bone && !parents)
+    return fail(STGCN_E_INVALID, "streams: null parents with a bone stream");
+  if (d->streams == STGCN_STREAM_JOINT)  // (J does not depend on score_channel)
+    return stgcn_input_stage_move(&d->in, src, clips, moves, x, status, stream);
+  if (!src || !clips || !x || !status)
+    return fail(STGCN_E_INVALID, "streams: null argument (src, clips, x, status)");
+  if (int rc = check_aligned({NP(x)}, 16)) return rc;
+  if (int rc = check_aligned({NP(src)}, d->in.src_f64 ? 8 : 4)) return rc;
+  if (int rc = check_aligned({NP(clips)}, 8)) return rc;
+  if (int rc = check_aligned({NP(status)}, 4)) return rc;
+  if (int rc = check_aligned({NP(moves)}, 8)) return rc;  // (null passes)
+  if (bone)
+    if (int rc = check_aligned({NP(parents)}, 4)) return rc;
+  const int bpc = blocks_per_clip(&d->in);
+  if (d->in.src_f64)
+    launch_streams<double>(d, src, clips, moves, bone ? parents : nullptr, x, status, bpc,
+                           (hipStream_t)stream);
+  else
+    launch_streams<float>(d, src, clips, moves, bone ? parents : nullptr, x, status, bpc,
+                          (hipStream_t)stream);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess)
+    return fail(STGCN_E_HIP, std::string("input_stage_streams launch: ") + hipGetErrorString(e));
   return STGCN_OK;
 }
 

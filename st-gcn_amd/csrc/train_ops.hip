@@ -534,7 +534,7 @@ int stgcn_seed_next(uint64_t *counter, uint64_t *token, void *stream) {
 int stgcn_features(void) {
   return STGCN_FEATURE_EVAL_CHAIN | STGCN_FEATURE_EVAL_HEAD | STGCN_FEATURE_STEP_STATE |
          STGCN_FEATURE_INPUT_STAGE | STGCN_FEATURE_OPTIMIZERS | STGCN_FEATURE_HEAD_LOSS |
-         STGCN_FEATURE_INPUT_MOVE | STGCN_FEATURE_BWD_OVERLAP;
+         STGCN_FEATURE_INPUT_MOVE | STGCN_FEATURE_BWD_OVERLAP | STGCN_FEATURE_INPUT_STREAMS;
 }
 
 int stgcn_head_fwd(const stgcn_head_desc_t *d, const float *y, const float *W, const float *bias,

@@ -30,7 +30,10 @@ transposes to NCTV, into a tensor the caller may own (a GraphedStep's input).
 On top of it ST-GCN's training augmentation, which the reference leaves as a
 TODO (augmentation.py:48): ``clip_moves`` / ``apply_moves_reference`` ("random
 moving": per-frame interpolated rotation, scale and translation, applied by
-the same kernel) and ``pack_clips(crop="random")`` ("random choose").
+the same kernel) and ``pack_clips(crop="random")`` ("random choose"); and the
+input views of the ST-GCN descendants, bone, joint motion and bone motion
+beside the joints (``STREAMS`` / ``streams_reference`` / ``stage_clips(streams=)``
+/ ``RaggedDeviceLoader(streams=)``), formed by that launch after the augmentation.
 """
 import ctypes
 import os
@@ -39,7 +42,7 @@ import random
 import numpy as np
 import torch
 
-from . import hip_lib
+from . import graph, hip_lib
 
 
 def pad_array_with_loops(x, target_len):
@@ -309,6 +312,78 @@ def apply_moves_reference(x_ntvc, moves):
     return out
 
 
+# STGCN_STREAM_* (include/stgcn_hip.h): the input views of the ST-GCN descendants
+# (2s-AGCN, ST-GCN++, PYSKL), by the names their recipes use. Whatever the order
+# they are asked for in, the channel groups of x come in bit order.
+STREAMS = {"j": hip_lib.STREAM_JOINT, "b": hip_lib.STREAM_BONE,
+           "jm": hip_lib.STREAM_JOINT_MOTION, "bm": hip_lib.STREAM_BONE_MOTION}
+_BONE_STREAMS = hip_lib.STREAM_BONE | hip_lib.STREAM_BONE_MOTION
+
+
+def parse_streams(streams):
+    """The STGCN_STREAM_* mask of "j", "b", "jm", "bm", a "+"-joined combination
+    ("j+b+jm+bm") or an iterable of those names; a mask passes through."""
+    if isinstance(streams, (int, np.integer)) and not isinstance(streams, bool):
+        if not 1 <= streams <= 15:
+            raise ValueError(f"streams: the mask {streams} is not a non-empty subset of 1 | 2 | "
+                             "4 | 8")
+        return int(streams)
+    names = streams.split("+") if isinstance(streams, str) else list(streams)
+    mask = 0
+    for name in names:
+        if not isinstance(name, str) or name.strip() not in STREAMS:
+            raise ValueError(f"streams: {name!r} is not one of {', '.join(STREAMS)}")
+        mask |= STREAMS[name.strip()]
+    if not mask:
+        raise ValueError("streams: at least one of " + ", ".join(STREAMS))
+    return mask
+
+
+def stream_count(mask):
+    """S: the number of streams of a mask (x has S * C channels)."""
+    return bin(mask).count("1")
+
+
+def streams_reference(j_nctv, parents, streams, score_channel=None):
+    """The stream kernel's arithmetic in numpy float32 (the CPU yardstick of
+    stgcn_input_stage_streams): the joint array J (N, C, T, V) float32 -> (N,
+    S * C, T, V) float32, the selected streams in bit order. With p = parents[v]:
+    bone B = J[.., v] - J[.., p]; joint motion J[t + 1] - J[t] and bone motion
+    B[t + 1] - B[t], 0 in the last frame; on ``score_channel`` (a confidence)
+    the mean (a + b) * 0.5 instead of each difference, the last frame of the
+    motion streams 0 there too. Every operation is one float32 operation."""
+    j = np.asarray(j_nctv)
+    if j.dtype != np.float32 or j.ndim != 4:
+        raise ValueError("streams_reference: J is an (N, C, T, V) float32 array")
+    mask = parse_streams(streams)
+    C, V = j.shape[1], j.shape[3]
+    if score_channel is not None and not (score_channel == C - 1 and score_channel >= 2):
+        raise ValueError(f"streams_reference: score_channel is None or C - 1 = {C - 1} (>= 2)")
+    half = np.float32(0.5)
+
+    def op(b, a):
+        out = b - a
+        if score_channel is not None:
+            out[:, score_channel] = (b[:, score_channel] + a[:, score_channel]) * half
+        return out
+
+    def motion(a):
+        out = np.zeros_like(a)
+        out[:, :, :-1] = op(a[:, :, 1:], a[:, :, :-1])
+        return out
+
+    bone = None
+    if mask & _BONE_STREAMS:
+        par = np.asarray(parents)
+        if par.shape != (V,) or ((par < 0) | (par >= V)).any():
+            raise ValueError(f"streams_reference: parents holds {V} joints of [0, {V})")
+        bone = op(j, j[:, :, :, par])
+    parts = [(hip_lib.STREAM_JOINT, lambda: j), (hip_lib.STREAM_BONE, lambda: bone),
+             (hip_lib.STREAM_JOINT_MOTION, lambda: motion(j)),
+             (hip_lib.STREAM_BONE_MOTION, lambda: motion(bone))]
+    return np.concatenate([f() for bit, f in parts if mask & bit], axis=1)
+
+
 def _np_dtype(dtype):
     if isinstance(dtype, torch.dtype):
         dtype = {torch.float32: np.float32, torch.float64: np.float64}.get(dtype, dtype)
@@ -384,7 +459,8 @@ def pack_clips(items, T_out, C_src, dtype, out=None, transforms=None, crop="firs
     return buf, table, labels
 
 
-def stage_clips(src, table, x, status, moves=None):
+def stage_clips(src, table, x, status, moves=None, streams=None, parents=None,
+                score_channel=None):
     """One stgcn_input_stage launch on the current stream: src (frames, V,
     C_src) fp32 / fp64 on the device (its first dimension is the capacity the
     kernel checks the table against), table the device copy of a CLIP_DTYPE
@@ -395,10 +471,36 @@ def stage_clips(src, table, x, status, moves=None):
     moves: the device copy of a MOVE_DTYPE table (any dtype, N * 160 bytes, read
     when the kernel runs like the clip table): the launch is
     stgcn_input_stage_move, which applies each clip's move after its matrix; an
-    invalid record adds 2 to status[n] and zeros the clip."""
+    invalid record adds 2 to status[n] and zeros the clip.
+    streams (``parse_streams``): the launch is stgcn_input_stage_streams and x is
+    (N, S * C, T_out, V), the S selected streams of C channels each in bit order
+    (joint, bone, joint motion, bone motion; ``streams_reference``). parents: a
+    contiguous int32 tensor of V entries on x's GPU (``graph.parents``), needed
+    with "b" or "bm" and read when the kernel runs; an entry outside [0, V) adds
+    4 to every status[n] and zeros x. score_channel: None, or C - 1 >= 2, the
+    confidence channel, averaged where the coordinates are subtracted."""
     if x.dtype != torch.float32 or x.dim() != 4 or not x.is_contiguous():
         raise ValueError("stage_clips: x is a contiguous (N, C, T_out, V) float32 tensor")
     N, C, T_out, V = x.shape
+    mask = None
+    if streams is None:
+        if parents is not None or score_channel is not None:
+            raise ValueError("stage_clips: parents and score_channel go with streams")
+    else:
+        mask = parse_streams(streams)
+        S = stream_count(mask)
+        if C % S:
+            raise ValueError(f"stage_clips: x has {C} channels, not a multiple of the {S} "
+                             "streams")
+        C //= S
+        # (a table is needed with a bone stream; one given without is checked all the
+        # same and not passed on)
+        if (parents is None and mask & _BONE_STREAMS) or (parents is not None and (
+                parents.dtype != torch.int32 or parents.dim() != 1 or
+                parents.numel() != V or not parents.is_contiguous() or
+                parents.device != x.device)):
+            raise ValueError(f"stage_clips: parents is a contiguous int32 tensor of {V} "
+                             "entries on x's GPU")
     if src.dtype not in (torch.float32, torch.float64) or src.dim() != 3 or \
             not src.is_contiguous() or src.shape[1] != V:
         raise ValueError(f"stage_clips: src is a contiguous (frames, {V}, C_src) float32 or "
@@ -411,15 +513,23 @@ def stage_clips(src, table, x, status, moves=None):
         raise ValueError("stage_clips: src, table, x and status live on one GPU")
     d = hip_lib.InputDesc(N, C, T_out, V, src.shape[2], int(src.dtype == torch.float64),
                           src.shape[0])
-    if moves is None:
+    if moves is None and mask is None:
         hip_lib.check(hip_lib.lib().stgcn_input_stage(
             ctypes.byref(d), hip_lib.ptr(src), hip_lib.ptr(table), hip_lib.ptr(x),
             hip_lib.ptr(status), hip_lib.stream_handle(x.device)))
         return x
-    if not moves.is_contiguous() or moves.device != x.device or \
-            moves.numel() * moves.element_size() < N * MOVE_DTYPE.itemsize:
+    if moves is not None and (
+            not moves.is_contiguous() or moves.device != x.device or
+            moves.numel() * moves.element_size() < N * MOVE_DTYPE.itemsize):
         raise ValueError(f"stage_clips: moves needs {N * MOVE_DTYPE.itemsize} contiguous bytes "
                          "on x's GPU")
+    if mask is not None:
+        sd = hip_lib.StreamsDesc(d, mask, -1 if score_channel is None else int(score_channel))
+        hip_lib.check(hip_lib.lib().stgcn_input_stage_streams(
+            ctypes.byref(sd), hip_lib.ptr(src), hip_lib.ptr(table), hip_lib.ptr(moves),
+            hip_lib.ptr(parents if mask & _BONE_STREAMS else None), hip_lib.ptr(x),
+            hip_lib.ptr(status), hip_lib.stream_handle(x.device)))
+        return x
     hip_lib.check(hip_lib.lib().stgcn_input_stage_move(
         ctypes.byref(d), hip_lib.ptr(src), hip_lib.ptr(table), hip_lib.ptr(moves), hip_lib.ptr(x),
         hip_lib.ptr(status), hip_lib.stream_handle(x.device)))
@@ -462,12 +572,24 @@ class RaggedDeviceLoader:
     longer than T_out gives a random window instead of its first T_out frames
     (``pack_clips``). Per batch the draws are: the matrices, the moves, the
     window starts. An invalid move record is reported like an invalid table
-    entry, once, after the last batch."""
+    entry, once, after the last batch.
+
+    streams (``parse_streams``, e.g. "j+b+jm+bm"): x has S * C channels, the S
+    selected streams of the augmented and moved clip in bit order, from the same
+    one launch (stgcn_input_stage_streams); out= is then (N, S * C, T_out, V).
+    parents (V entries; default ``graph.parents(graph.graph_for(V))``) is
+    uploaded once, on the side stream; score_channel as in ``stage_clips``. A
+    parents table the kernel refuses is reported once, after the last batch."""
 
     def __init__(self, batches_of_items, device, V, C, C_src, T_out=None,
                  src_dtype=torch.float32, augment=False, out=None, labels_out=None,
-                 move=False, crop="first"):
+                 move=False, crop="first", streams=None, parents=None, score_channel=None):
         self.batches, self.device = batches_of_items, torch.device(device)
+        if streams is None and (parents is not None or score_channel is not None):
+            raise ValueError("RaggedDeviceLoader: parents and score_channel go with streams")
+        self.streams = None if streams is None else parse_streams(streams)
+        self.score_channel = score_channel
+        S = 1 if streams is None else stream_count(self.streams)
         if crop not in ("first", "random"):
             raise ValueError(f"RaggedDeviceLoader: crop is 'first' or 'random', not {crop!r}")
         self.move, self.crop = bool(move), crop
@@ -477,18 +599,39 @@ class RaggedDeviceLoader:
         self.out, self.labels_out = out, labels_out
         if (out is not None or labels_out is not None) and T_out is None:
             raise ValueError("RaggedDeviceLoader: out / labels_out need a fixed T_out")
-        if out is not None and (tuple(out.shape[1:]) != (C, T_out, V) or
+        if out is not None and (tuple(out.shape[1:]) != (S * C, T_out, V) or
                                 out.dtype != torch.float32 or not out.is_contiguous()):
-            raise ValueError(f"RaggedDeviceLoader: out is a contiguous (N, {C}, {T_out}, {V}) "
+            raise ValueError(f"RaggedDeviceLoader: out is a contiguous (N, {S * C}, {T_out}, {V}) "
                              "float32 tensor")
         d = hip_lib.InputDesc(1, C, T_out or 1, V, C_src, int(src_dtype == torch.float64), 1)
         lib = hip_lib.load_library()
-        check = lib.stgcn_input_move_check if self.move else lib.stgcn_input_check
-        if check(ctypes.byref(d)) != 0:
+        if self.streams is not None:
+            sd = hip_lib.StreamsDesc(d, self.streams,
+                                     -1 if score_channel is None else int(score_channel))
+            rc = lib.stgcn_input_streams_check(ctypes.byref(sd))
+        else:
+            check = lib.stgcn_input_move_check if self.move else lib.stgcn_input_check
+            rc = check(ctypes.byref(d))
+        if rc != 0:
             raise ValueError("RaggedDeviceLoader: " +
                              lib.stgcn_last_error().decode(errors="replace"))
         self.stream = torch.cuda.Stream(self.device)
         self.slots = (_Slot(), _Slot())
+        self.parents = self.parents_host = self.parents_copied = None
+        if parents is not None and np.shape(parents) != (V,):
+            raise ValueError(f"RaggedDeviceLoader: parents holds {V} entries, got "
+                             f"{np.shape(parents)}")
+        if self.streams is not None and self.streams & _BONE_STREAMS:
+            if parents is None:
+                parents = graph.parents(graph.graph_for(V))
+            par = np.ascontiguousarray(parents, dtype=np.int32)
+            # uploaded once, on the side stream like the slots' buffers; the first
+            # stage kernel of every iteration waits for the copy
+            self.parents_host = torch.from_numpy(par).pin_memory()
+            with torch.cuda.stream(self.stream):
+                self.parents = self.parents_host.to(self.device, non_blocking=True)
+                self.parents_copied = torch.cuda.Event()
+                self.parents_copied.record(self.stream)
 
     def _stage(self, items, slot):
         """Packs ``items`` into the slot and starts its copies on the side stream."""
@@ -556,15 +699,20 @@ class RaggedDeviceLoader:
                                      f"{self.out.shape[0]}")
                 x = self.out
             else:
-                x = torch.empty((N, self.C, T_out, self.V), dtype=torch.float32,
+                S = 1 if self.streams is None else stream_count(self.streams)
+                x = torch.empty((N, S * self.C, T_out, self.V), dtype=torch.float32,
                                 device=self.device)
+            if self.parents is not None:
+                cur.wait_event(self.parents_copied)
+                self.parents.record_stream(cur)
             status = torch.empty(N, dtype=torch.int32, device=self.device)
             cap = slot.dev.numel() // (self.V * self.C_src)
             src = slot.dev[:cap * self.V * self.C_src].view(cap, self.V, self.C_src)
             nc = N * CLIP_DTYPE.itemsize
             stage_clips(src, slot.dev_table, x, status,
                         moves=slot.dev_table[nc:nc + N * MOVE_DTYPE.itemsize] if self.move
-                        else None)
+                        else None, streams=self.streams, parents=self.parents,
+                        score_channel=self.score_channel)
             slot.free = torch.cuda.Event()
             slot.free.record(cur)
             statuses.append(status)
@@ -573,6 +721,9 @@ class RaggedDeviceLoader:
                 yd = self.labels_out
             yield x, yd
         flags = torch.cat(statuses).cpu()  # (the one host read)
+        if (flags & 4).any():
+            raise RuntimeError("RaggedDeviceLoader: invalid parents table (an entry outside "
+                               f"[0, {self.V})): every clip was staged as zeros")
         for bit, what in ((1, "clip table entries"), (2, "move records")):
             bad = (flags & bit).nonzero().flatten().tolist()
             if bad:

@@ -113,6 +113,41 @@ def graph_for(num_joints):
     raise ValueError(f"no skeleton graph defined for V={num_joints}")
 
 
+# The roots of the bone stream (data.STREAMS): joint 1, the neck, ST-GCN's centre
+# joint in both layouts; one per person.
+_ROOTS = {"coco18": (1,), "body25": (1,), "body25x2": (1, 26)}
+
+
+def parents(graph, roots=None):
+    """(V,) int32: the parent of every joint on its path to a root, by
+    breadth-first search from ``roots`` (default: the neck of each person of
+    the graphs defined here); a root is its own parent. The bone stream is
+    joint minus parent joint. The graphs here are trees per person, so the
+    result does not depend on the visit order. Raises when a joint cannot be
+    reached from the roots."""
+    V = graph.num_joints
+    if roots is None:
+        if graph.name not in _ROOTS:
+            raise ValueError(f"parents: no default roots for the graph {graph.name!r}")
+        roots = _ROOTS[graph.name]
+    roots = [int(r) for r in roots]
+    if not roots or any(not 0 <= r < V for r in roots):
+        raise ValueError(f"parents: the roots {roots} are not joints of a {V}-joint graph")
+    out = np.full(V, -1, dtype=np.int32)
+    out[roots] = roots
+    queue = list(roots)
+    while queue:
+        cur = queue.pop(0)
+        for nb in graph.adj_list[cur]:
+            if out[nb] < 0:
+                out[nb] = cur
+                queue.append(nb)
+    if (out < 0).any():
+        raise ValueError(f"parents: the joints {np.flatnonzero(out < 0).tolist()} of "
+                         f"{graph.name!r} cannot be reached from the roots {roots}")
+    return out
+
+
 def increase_neighbourhood(graph, neighbour_elements, open_elements):
     """One DFS expansion step (``src/data/adjacency.py:13-32``).
 

@@ -41,6 +41,8 @@ FEATURE_OPTIMIZERS = 16  # stgcn_opt_*: AdamW, AMSGrad (train_ops.FusedAdam / Fu
 FEATURE_HEAD_LOSS = 32  # stgcn_loss_check, stgcn_head_eval_loss / _u (train_ops.head_eval)
 FEATURE_INPUT_MOVE = 64  # stgcn_input_move_check / stgcn_input_stage_move (data.clip_moves)
 FEATURE_BWD_OVERLAP = 128  # stgcn_bwd_overlap: the backward's small kernels beside its GEMMs
+FEATURE_INPUT_STREAMS = 256  # stgcn_input_streams_check / stgcn_input_stage_streams (data.STREAMS)
+STREAM_JOINT, STREAM_BONE, STREAM_JOINT_MOTION, STREAM_BONE_MOTION = 1, 2, 4, 8
 LOSS_WEIGHT = 1  # stgcn_loss_desc_t.flags: class_weight is given
 OPT_ADAM = 1  # stgcn_opt_desc_t.algo
 OPT_DECOUPLED_WD, OPT_AMSGRAD = 2, 4  # stgcn_opt_desc_t.flags
@@ -153,6 +155,13 @@ class Move(ctypes.Structure):  # stgcn_move_t, 160 bytes (numpy: data.MOVE_DTYPE
 
 assert ctypes.sizeof(Move) == 160 and Move.angle.offset == 24 and Move.ty.offset == 120
 
+
+class StreamsDesc(ctypes.Structure):  # stgcn_streams_desc_t (FEATURE_INPUT_STREAMS), 40 bytes
+    _fields_ = [("inp", InputDesc), ("streams", _c_int), ("score_channel", _c_int)]
+
+
+assert ctypes.sizeof(StreamsDesc) == 40 and StreamsDesc.streams.offset == 32
+
 # Every symbol include/stgcn_hip.h declares (checked by tests/test_capi.py).
 EXPORTED = ("stgcn_abi_version", "stgcn_last_error", "stgcn_check_desc",
             "stgcn_fwd_workspace_bytes", "stgcn_bwd_workspace_bytes",
@@ -168,7 +177,8 @@ EXPORTED = ("stgcn_abi_version", "stgcn_last_error", "stgcn_check_desc",
             "stgcn_grad_norm", "stgcn_input_check", "stgcn_input_stage", "stgcn_opt_check",
             "stgcn_opt_table_bytes", "stgcn_opt_build_table", "stgcn_opt_step",
             "stgcn_loss_check", "stgcn_head_eval_loss", "stgcn_head_eval_loss_u",
-            "stgcn_input_move_check", "stgcn_input_stage_move", "stgcn_bwd_overlap")
+            "stgcn_input_move_check", "stgcn_input_stage_move", "stgcn_bwd_overlap",
+            "stgcn_input_streams_check", "stgcn_input_stage_streams")
 
 _LIB = None
 
@@ -284,6 +294,11 @@ def load_library(path=LIB_PATH):
     lib.stgcn_input_move_check.restype = ctypes.c_int
     lib.stgcn_input_stage_move.argtypes = [ctypes.POINTER(InputDesc), _vp, _vp, _vp, _vp, _vp, _vp]
     lib.stgcn_input_stage_move.restype = ctypes.c_int
+    lib.stgcn_input_streams_check.argtypes = [ctypes.POINTER(StreamsDesc)]
+    lib.stgcn_input_streams_check.restype = ctypes.c_int
+    lib.stgcn_input_stage_streams.argtypes = [ctypes.POINTER(StreamsDesc), _vp, _vp, _vp, _vp, _vp,
+                                              _vp, _vp]
+    lib.stgcn_input_stage_streams.restype = ctypes.c_int
     lib.stgcn_bwd_overlap.argtypes = [ctypes.c_int]
     lib.stgcn_bwd_overlap.restype = ctypes.c_int
     if lib.stgcn_abi_version() != ABI_VERSION:
