@@ -64,6 +64,27 @@
  *         grad / s0 / s1 / s2 of a table entry, lr_dev, grad_coef and step_dev 4.
  *     A caller with a misaligned read-only input for a 16-byte argument passes an
  *     aligned copy (the Python binding does); torch.empty results are aligned.
+ *   - Non-finite values. A NaN or +-Inf in an input is never turned into a
+ *     finite wrong value. Against the reference's dense IEEE arithmetic, per
+ *     output element: (a) where the reference is non-finite and the element
+ *     lies in the footprint that sparse arithmetic reaches from the bad element
+ *     (same clip, every output channel, output frames t' with
+ *     |t' * stride - t| <= 4, joints v' with A[k][v'][v] != 0 for some k; the
+ *     transposed set for a bad dy in the eval-mode backward), the result is
+ *     non-finite; NaN and +-Inf are interchangeable (the fp16 / bf16 operand
+ *     splits turn Inf into NaN). (b) Where the reference is finite the result
+ *     is the usual one, or it is non-finite inside the dense footprint (the
+ *     same frames at every joint): a dense 0 * NaN is NaN, a kernel that skips
+ *     A's zeros gives a number, and ReLU(-Inf) = 0. (c) With running statistics
+ *     (training = 0) every other clip is untouched, in every GEMM mode: the
+ *     f16x2 operand bounds (max |x| words) are taken over finite elements only,
+ *     and the BatchNorm backward's batch-mean terms are absent, not multiplied
+ *     by 0. In training mode one bad element makes the batch statistics, and
+ *     with them y, the gradients and the running statistics, non-finite.
+ *     ReLU keeps NaN and its backward is a select (a bad dy under a closed ReLU
+ *     reaches nothing). stgcn_grad_norm gives a NaN coef_out for a NaN norm
+ *     (every clipped gradient is then NaN, as with clip_grad_norm_), 0 for an
+ *     Inf norm; AMSGrad's running maximum keeps a NaN.
  *   - A is (K,V,V), W is (K*C_out, C_in) (the reference's 1x1 Conv2d weight),
  *     Wt is (C_out, C_out, 9) (the (9,1) Conv2d weight).
  *   - The workspace is caller-allocated (query *_workspace_bytes first); the

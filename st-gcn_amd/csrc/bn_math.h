@@ -36,7 +36,13 @@ __device__ __forceinline__ BnAff bn_aff(const BnRef &bn, int c) {
   return bn_aff(bn.mean, bn.invstd, bn.g, bn.b, c);
 }
 
-// The element of y = ReLU(BN2(u)): y, the mask m = y > 0 and uhat, as
+// ReLU keeps NaN, as torch.relu does (stgcn_hip.h Conventions, "Non-finite
+// values"): its predicate is !(t <= 0), true for NaN, and y and the backward's
+// mask come from that one predicate so that they cannot disagree. On every
+// other value it is t > 0, and the bits of y are those of t > 0 ? t : 0.
+__device__ __forceinline__ bool relu_on(float t) { return !(t <= 0.f); }
+
+// The element of y = ReLU(BN2(u)): y, the mask m = relu_on(pre) and uhat, as
 // bn_relu_fwd_body (kernels_bn.hip) forms the block's output. A kernel that
 // rebuilds that output from U writes these lines on bn_pre / bn_hat, or
 // bn_relu(pre(u)) where only y is needed.
@@ -48,16 +54,20 @@ __device__ __forceinline__ BnReluX bn_relu_x(const BnAff &p, float u) {
   BnReluX r;
   const float t = p.pre(u);
   r.uh = p.hat(u);
-  r.m = t > 0.f;
+  r.m = relu_on(t);
   r.x = r.m ? t : 0.f;
   return r;
 }
-__device__ __forceinline__ float bn_relu(float t) { return t > 0.f ? t : 0.f; }
+__device__ __forceinline__ float bn_relu(float t) { return relu_on(t) ? t : 0.f; }
+// The same values from one instruction (v_maximum3_f32: the IEEE 754-2019
+// maximum, which keeps NaN and gives +0 for -0), for the sites that need no
+// mask: BN1's ReLU of the residual block and the convolutions' ReLU epilogue.
+__device__ __forceinline__ float relu_max(float t) { return __builtin_elementwise_maximum(t, 0.f); }
 
 // ReLU + BN2 backward element: g = d on the mask, mg = sum(g) / M, mgu = sum(g uhat) / M
 __device__ __forceinline__ float bn2_bwd(const BnAff &p, float u, float d, float mg, float mgu) {
   const float uh = p.hat(u);
-  const float gg = p.pre(u) > 0.f ? d : 0.f;
+  const float gg = relu_on(p.pre(u)) ? d : 0.f;
   return p.a * (gg - mg - uh * mgu);
 }
 

@@ -109,6 +109,16 @@ __device__ __forceinline__ float wave_sumf(float v) {
 // add one atomicMax per workgroup to slot blockIdx % kAmaxSlots (thousands of
 // workgroups on ONE word serialise in L2: 3.4 ms per cfg2 step measured),
 // readers take the max over the slots (amax_read).
+// The bound is that of the finite elements: a producer adds amax_abs(v), which
+// is 0 for a non-finite v, so every word stays at or below the largest finite
+// float. (fmaxf drops a NaN by itself; an Inf would take the word, f16x2_se
+// would clamp the scale at 2^-100 and every finite element of the tensor, the
+// clips the Inf has nothing to do with included, would underflow to 0 in fp16.
+// The Inf itself needs no bound: Inf * 2^se is Inf and propagates.)
+__device__ __forceinline__ float amax_abs(float v) {
+  const float a = fabsf(v);
+  return a < __builtin_inff() ? a : 0.f;
+}
 
 __device__ __forceinline__ unsigned amax_read(const unsigned *amax) {
   unsigned m = 0;
@@ -429,7 +439,7 @@ __device__ __forceinline__ void conv_tile_epilogue(const ConvGemmParams &p, floa
             val += P.rs[ii * 4 + j];
           else if (p.res)
             val += __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_res, off, 0, 0));
-          if (p.relu_out) val = fmaxf(val, 0.f);
+          if (p.relu_out) val = relu_max(val);
           if constexpr (DROP) {
             if (ok)
               val = dropout_keep(drop, (uint64_t)n * p.out_bstride + row * ostride + ocol[j])
@@ -607,7 +617,7 @@ __device__ __forceinline__ void conv_tile_store_rows_t(const ConvGemmParams &p, 
       float val = v[e] + br;
       if (p.bias_rv && ok) val += sbv[r * V + col % V];
       val += rv[e];
-      if (p.relu_out) val = fmaxf(val, 0.f);
+      if (p.relu_out) val = relu_max(val);
       if constexpr (DROP) {
         if (ok) val = dropout_keep(drop, (uint64_t)(obase + col)) ? val * drop.scale : 0.f;
       }

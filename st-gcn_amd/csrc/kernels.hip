@@ -85,7 +85,7 @@ __global__ __launch_bounds__(256) void k_gather_fwd(const float *x, const float 
     const BnAff bn = bn_aff(mean, invstd, g, b, ci);
     for (int i = threadIdx.x; i < tc * V; i += 256) {
       const float t = bn.pre(src[i]);
-      xs[i] = relu ? fmaxf(t, 0.f) : t;
+      xs[i] = relu ? relu_max(t) : t;
     }
     __syncthreads();
     for (int o = threadIdx.x; o < nout; o += 256) {
@@ -97,7 +97,7 @@ __global__ __launch_bounds__(256) void k_gather_fwd(const float *x, const float 
       float s = 0.f;
       for (int w = 0; w < V; ++w) s = fmaf(ar[w], xr[w], s);
       G[(((int64_t)n * K + k) * C + ci) * L + (int64_t)(t0 + t) * V + v] = s;
-      gm = fmaxf(gm, fabsf(s));
+      gm = fmaxf(gm, amax_abs(s));
     }
   }
   if (amax) block_amax<256>(gm, amax);
@@ -146,7 +146,7 @@ __global__ __launch_bounds__(256) void k_gather3(const float *__restrict__ x,
 #pragma unroll
   for (int w = 0; w < VP; ++w) {
     const float t = w < V ? bn.pre(xr[w]) : 0.f;
-    xv[w] = relu ? fmaxf(t, 0.f) : t;
+    xv[w] = relu ? relu_max(t) : t;
   }
   for (int k = 0; k < K; ++k) {
     float *gout = G + ((n * K + k) * C + ci) * (int64_t)T * V + (int64_t)t * V;
@@ -163,7 +163,7 @@ __global__ __launch_bounds__(256) void k_gather3(const float *__restrict__ x,
         acc = fmaf(q.w, xv[w4 + 3], acc);
       }
       if (live) gout[v] = acc;
-      gm = fmaxf(gm, fabsf(acc));
+      gm = fmaxf(gm, amax_abs(acc));
     }
   }
   if (amax) block_amax<256>(gm, amax);
@@ -220,7 +220,7 @@ __global__ __launch_bounds__(256) void k_gather4(const float *__restrict__ x,
     float xx = w < V ? xs[tid * V + w] : 0.f;
     if (prev) xx = bn_relu(bn_pre(xx, pmu, pa, pbe));
     const float t = w < V ? bn_pre(xx, mu, a, be) : 0.f;
-    xv[w] = relu ? fmaxf(t, 0.f) : t;
+    xv[w] = relu ? relu_max(t) : t;
   }
   for (int k = 0; k < K; ++k) {
     const float *Ak = As + k * V * VP;
@@ -243,7 +243,8 @@ __global__ __launch_bounds__(256) void k_gather4(const float *__restrict__ x,
     for (int e = tid; e < BF / 4; e += 256) {
       const float4 q = *reinterpret_cast<const float4 *>(os + e * 4);
       *reinterpret_cast<float4 *>(dst + e * 4) = q;
-      gm = fmaxf(gm, fmaxf(fmaxf(fabsf(q.x), fabsf(q.y)), fmaxf(fabsf(q.z), fabsf(q.w))));
+      gm = fmaxf(gm, fmaxf(fmaxf(amax_abs(q.x), amax_abs(q.y)),
+                           fmaxf(amax_abs(q.z), amax_abs(q.w))));
     }
   }
   if (amax) block_amax<256>(gm, amax);
@@ -326,7 +327,7 @@ __global__ __launch_bounds__(256) void k_spatial_bwd3(
       s += acc[w];
       sn = fmaf(acc[w], xn, sn);
       if (write_dx) dxr[w] = acc[w];
-      XBs[tid * VP + w] = relu ? fmaxf(bn, 0.f) : bn;
+      XBs[tid * VP + w] = relu ? relu_max(bn) : bn;
     }
   } else {
     for (int k = 0; k < K; ++k)
@@ -612,7 +613,7 @@ __global__ __launch_bounds__(bwd5_nw(KMAX) * 64) void k_spatial_bwd5(
           if (pv) {
             const float t = bn_pre(xv, pmu, pa, pb);
             uh = bn_hat(xv, pmu, pis);
-            pm = t > 0.f;
+            pm = relu_on(t);
             xv = pm ? t : 0.f;
           }
           float d = NH == 2 ? dxs[rl * V + w] + dxs2[rl * V + w] : dxs[rl * V + w];
@@ -625,7 +626,7 @@ __global__ __launch_bounds__(bwd5_nw(KMAX) * 64) void k_spatial_bwd5(
             sv[2] += d;
             sv[3] = fmaf(d, uh, sv[3]);
           }
-          xs[rl * V + w] = relu ? fmaxf(bn, 0.f) : bn;
+          xs[rl * V + w] = relu ? relu_max(bn) : bn;
         }
       }
       STGCN_ROWPASS_SUMS(sv, ns, seg, ci);
@@ -894,7 +895,7 @@ __global__ __launch_bounds__(512, 1) void k_spatial_bwd6(
           if (pv) {  // prev mode: the staged plane is the previous block's U (see bwd5)
             const float t = bn_pre(xv, pmu, pa, pb);
             uh = bn_hat(xv, pmu, pis);
-            pm = t > 0.f;
+            pm = relu_on(t);
             xv = pm ? t : 0.f;
           }
           float d = dxs[rl * V + w] + dxs2[rl * V + w];
@@ -907,7 +908,7 @@ __global__ __launch_bounds__(512, 1) void k_spatial_bwd6(
             sv[2] += d;
             sv[3] = fmaf(d, uh, sv[3]);
           }
-          const float f = relu ? fmaxf(bn, 0.f) : bn;
+          const float f = relu ? relu_max(bn) : bn;
           const __bf16 fh = (__bf16)f;
           __bf16 *xt = reinterpret_cast<__bf16 *>(XT) + w * XTP + rl;
           xt[0] = fh;
@@ -1079,7 +1080,7 @@ __global__ __launch_bounds__(256, 2) void k_gather_mfma(
     for (int s2 = 0; s2 < VH; ++s2) {
       const int w = 2 * s2 + hi;
       const float t = w < V ? bn.pre(xs[row * V + w]) : 0.f;
-      fv[s2] = w < V ? (relu ? fmaxf(t, 0.f) : t) : 0.f;
+      fv[s2] = w < V ? (relu ? relu_max(t) : t) : 0.f;
     }
 #pragma unroll
     for (int k = 0; k < KMAX; ++k) {
@@ -1338,7 +1339,7 @@ __global__ __launch_bounds__(256) void k_spatial_dx(const float *H, const float 
     const BnAff bn = bn_aff(mean, invstd, g, b, ci);
     for (int i = tid; i < tc * V; i += 256) {
       const float t = bn.pre(x[xo + i]);
-      xb[i] = relu ? fmaxf(t, 0.f) : t;
+      xb[i] = relu ? relu_max(t) : t;
     }
     for (int i = tid; i < K * tc * V; i += 256) {
       const int k = i / (tc * V), rem = i - k * tc * V;

@@ -67,6 +67,14 @@ static int slice_vec(int L, std::initializer_list<const void *> ptrs) {
       hipLaunchKernelGGL((kern<1>), grid, dim3(256), 0, s, __VA_ARGS__); \
   } while (0)
 
+// sum * invM of a BatchNorm backward's batch-mean terms. Eval mode passes
+// invM = 0 (constant running statistics: the terms are absent), and absent
+// means 0 whatever the sum holds: NaN * 0 is NaN, and one bad element of dy
+// would reach every clip through its channel's sum.
+__device__ __forceinline__ float bn_mean_term(double sum, double invM) {
+  return invM != 0.0 ? (float)(sum * invM) : 0.f;
+}
+
 // (amax, or null: max |x| as float bits, device_common.h block_amax -- the
 // fp16 operand bound of the folded block's GEMMs that read x, capi.hip fold_bna)
 template <int VEC>
@@ -84,7 +92,7 @@ __global__ __launch_bounds__(256) void k_bn_stats(const float *x, int C, int L, 
     for (int j = 0; j < VEC; ++j) {
       s += (double)v[j];
       q += (double)v[j] * (double)v[j];
-      m = fmaxf(m, fabsf(v[j]));
+      m = fmaxf(m, amax_abs(v[j]));
     }
   }
   if (amax) block_amax<256>(m, amax);
@@ -218,7 +226,7 @@ __device__ __forceinline__ void bn_relu_fwd_body(const float *U, const float *me
       if (drop.thresh) v[j] = dropout_keep(drop, base + i + j) ? v[j] * drop.scale : 0.f;
       s += (double)v[j];
       q += (double)v[j] * (double)v[j];
-      ym = fmaxf(ym, v[j]);
+      ym = fmaxf(ym, amax_abs(v[j]));  // (v >= 0 or NaN)
       if (yext && e.m) {
         cnt += 1.0;
         su += (double)e.uh;
@@ -315,7 +323,7 @@ __global__ __launch_bounds__(256) void k_bn_relu_bwd_reduce(const float *dy, con
     }
 #pragma unroll
     for (int j = 0; j < VEC; ++j)
-      if (bn.pre(u[j]) > 0.f) {
+      if (relu_on(bn.pre(u[j]))) {
         s += d[j];
         q += (double)d[j] * (double)bn.hat(u[j]);
       }
@@ -357,7 +365,7 @@ __global__ __launch_bounds__(256) void k_bn_relu_bwd_apply(
   const float dv = dync ? dync[(int64_t)n * C + c] : 0.f;  // (ABI 10: dy constant per row)
   drop = dropout_resolve(drop);
   const BnAff bn = bn_aff(mean, invstd, g, b, c);
-  const float mg = (float)(sg[c] * invM), mgu = (float)(sgu[c] * invM);
+  const float mg = bn_mean_term(sg[c], invM), mgu = bn_mean_term(sgu[c], invM);
   DyCoef dc = {};
   if (dy_coef) dc.load(dy_coef, C, c);
   double s = 0.0;
@@ -424,7 +432,7 @@ __global__ __launch_bounds__(256) void k_bn_relu_bwd_apply_cols(
   const int nz = gridDim.z, per = (N + nz - 1) / nz;
   const int n0 = blockIdx.z * per, n1 = min(N, n0 + per);
   const BnAff bn = bn_aff(mean, invstd, g, b, c);
-  const float mg = (float)(sg[c] * invM), mgu = (float)(sgu[c] * invM);
+  const float mg = bn_mean_term(sg[c], invM), mgu = bn_mean_term(sgu[c], invM);
   // (this kernel keeps the five loads as scalars: as a DyCoef captured by the
   // lambdas below they come out in other registers)
   float ca = 0.f, cmd = 0.f, cmu = 0.f, cis = 0.f, cmdn = 0.f;
@@ -487,7 +495,7 @@ __global__ __launch_bounds__(256) void k_bn_relu_bwd_apply_cols(
         o[j] = bn2_bwd(bn, u[j], d[j], mg, mgu);
         s += o[j];
         col[j] += o[j];
-        om = fmaxf(om, fabsf(o[j]));
+        om = fmaxf(om, amax_abs(o[j]));
       }
       if (du_bf16) {
         STGCN_STORE_DU_BF16(dU, base, i, o);
@@ -540,7 +548,7 @@ __global__ __launch_bounds__(256) void k_bn_relu_bwd_apply_fr(
   const int nz = gridDim.z, per = (N + nz - 1) / nz;
   const int n0 = blockIdx.z * per, n1 = min(N, n0 + per);
   const BnAff bn = bn_aff(mean, invstd, g, b, c);
-  const float mg = (float)(sg[c] * invM), mgu = (float)(sgu[c] * invM);
+  const float mg = bn_mean_term(sg[c], invM), mgu = bn_mean_term(sgu[c], invM);
   DyCoef dc = {};
   if (dy_coef) dc.load(dy_coef, C, c);
   // this thread's two output positions of dUA and their columns of A
@@ -571,7 +579,7 @@ __global__ __launch_bounds__(256) void k_bn_relu_bwd_apply_fr(
         if (drop.thresh) d[j] = dropout_keep(drop, base + pp + j) ? d[j] * drop.scale : 0.f;
         o[j] = bn2_bwd(bn, u[j], d[j], mg, mgu);
         s += o[j];
-        om = fmaxf(om, fabsf(o[j]));
+        om = fmaxf(om, amax_abs(o[j]));
       }
       col0 += o[0];
       col1 += o[1];
@@ -585,7 +593,7 @@ __global__ __launch_bounds__(256) void k_bn_relu_bwd_apply_fr(
 #pragma unroll
       for (int v = 1; v < V; ++v) t = fmaf(r[v], a0[v], t);
       dUA[base + e0] = t;
-      oma = fmaxf(oma, fabsf(t));
+      oma = fmaxf(oma, amax_abs(t));
     }
     if (e1 < np) {
       const float *r = obn + fr1 * V;
@@ -593,7 +601,7 @@ __global__ __launch_bounds__(256) void k_bn_relu_bwd_apply_fr(
 #pragma unroll
       for (int v = 1; v < V; ++v) t = fmaf(r[v], a1[v], t);
       dUA[base + e1] = t;
-      oma = fmaxf(oma, fabsf(t));
+      oma = fmaxf(oma, amax_abs(t));
     }
   }
   if (pok) {
@@ -716,7 +724,7 @@ __global__ __launch_bounds__(256) void k_bn1_bwd_apply(float *dx, const float *x
   const int c = blockIdx.x, n = blockIdx.y;
   const int64_t base = ((int64_t)n * C + c) * L;
   const float mu = mean[c], is = invstd[c], a = is * g[c];
-  const float md = (float)(sd[c] * invM), mdn = (float)(sdn[c] * invM);
+  const float md = bn_mean_term(sd[c], invM), mdn = bn_mean_term(sdn[c], invM);
   const float pg = pg2 ? pg2[c] : 1.f, pb = pg2 ? pb2[c] : 0.f;
   // poorly conditioned reconstruction (or g2 == 0 / non-finite): use U
   const bool from_u = pg2 && pU && !(fabsf(pb) <= 4.f * fabsf(pg));
@@ -741,14 +749,14 @@ __global__ __launch_bounds__(256) void k_bn1_bwd_apply(float *dx, const float *x
       vld<VEC>(pU + base + i, u);
 #pragma unroll
       for (int j = 0; j < VEC; ++j)
-        if (pbn.pre(u[j]) > 0.f) {
+        if (relu_on(pbn.pre(u[j]))) {
           s += d[j];
           q += (double)d[j] * (double)pbn.hat(u[j]);
         }
     } else if (pg2) {
 #pragma unroll
       for (int j = 0; j < VEC; ++j)
-        if (xv[j] > 0.f) {
+        if (relu_on(xv[j])) {
           s += d[j];
           q += (double)d[j] * (double)((xv[j] - pb) / pg);
         }
@@ -782,7 +790,7 @@ __global__ __launch_bounds__(256) void k_relu_bwd(const float *dy, const float *
     vld<VEC>(y + base + i, yv);
 #pragma unroll
     for (int j = 0; j < VEC; ++j) {
-      d[j] = yv[j] > 0.f ? d[j] * scale : 0.f;
+      d[j] = relu_on(yv[j]) ? d[j] * scale : 0.f;
       s += d[j];
     }
     vst<VEC>(dout + base + i, d);

@@ -211,7 +211,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_gemm(ConvGemmParams p) {
           float val = acc[j][i] + br;
           if (p.bias_rv) val += pbv[i & 1][j];
           if (p.res) val += prs[i & 1][j];
-          if (p.relu_out) val = fmaxf(val, 0.f);
+          if (p.relu_out) val = relu_max(val);
           if constexpr (DROP)
             val = dropout_keep(drop, (uint64_t)n * p.out_bstride + row * ostride + ocol[j])
                       ? val * drop.scale

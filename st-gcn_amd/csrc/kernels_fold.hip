@@ -537,11 +537,12 @@ __global__ __launch_bounds__(256) void k_absmax(const float *x, int64_t n, unsig
     const int64_t n4 = n / 4;
     for (int64_t i = i0; i < n4; i += stride) {
       const float4 v = reinterpret_cast<const float4 *>(x)[i];
-      m = fmaxf(m, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
+      m = fmaxf(m, fmaxf(fmaxf(amax_abs(v.x), amax_abs(v.y)),
+                         fmaxf(amax_abs(v.z), amax_abs(v.w))));
     }
-    for (int64_t i = n4 * 4 + i0; i < n; i += stride) m = fmaxf(m, fabsf(x[i]));
+    for (int64_t i = n4 * 4 + i0; i < n; i += stride) m = fmaxf(m, amax_abs(x[i]));
   } else {
-    for (int64_t i = i0; i < n; i += stride) m = fmaxf(m, fabsf(x[i]));
+    for (int64_t i = i0; i < n; i += stride) m = fmaxf(m, amax_abs(x[i]));
   }
   block_amax<256>(m, amax);
 }
@@ -881,7 +882,7 @@ __global__ __launch_bounds__(256) void k_absmax_multi(AmaxJobs js) {
   const AmaxJob &q = js.j[blockIdx.y];
   float m = 0.f;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < q.n; i += (int64_t)gridDim.x * 256)
-    m = fmaxf(m, fabsf(q.x[i]));
+    m = fmaxf(m, amax_abs(q.x[i]));
   __shared__ float wmax[4];
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));

@@ -198,10 +198,10 @@ __global__ __launch_bounds__(256, 2) void k_sp_fwd_bf16(SpFwdParams P) {
           float xx = st[k];
           if (P.pbn.mean) {
             const float u = (xx - tb[48 + ch]) * tb[64 + ch] + tb[80 + ch];
-            xx = u > 0.f ? u : 0.f;
+            xx = bn_relu(u);
           }
           v = (xx - tb[ch]) * tb[16 + ch] + tb[32 + ch];
-          if (P.relu) v = fmaxf(v, 0.f);
+          if (P.relu) v = relu_max(v);
         }
         xi[loff[k]] = (__bf16)v;
       }
@@ -445,10 +445,10 @@ __global__ __launch_bounds__(512, 1) void k_sp_fwd_wide(SpFwdParams P) {
           float xx = st[k];
           if (P.pbn.mean) {
             const float u = (xx - tb[48 + ch]) * tb[64 + ch] + tb[80 + ch];
-            xx = u > 0.f ? u : 0.f;
+            xx = bn_relu(u);
           }
           v = (xx - tb[ch]) * tb[16 + ch] + tb[32 + ch];
-          if (P.relu) v = fmaxf(v, 0.f);
+          if (P.relu) v = relu_max(v);
         }
         xi[(t * 16 + ch) * G::XP + w] = (__bf16)v;
       }

@@ -340,7 +340,7 @@ __global__ __launch_bounds__(512, 1) void k_sp_bwd_fused(SpBwdParams P) {
         if (pv) {
           const float t = (xq[q] - pmu) * pa + pb;
           uh = (xq[q] - pmu) * pis;
-          pm = t > 0.f;
+          pm = relu_on(t);
           xq[q] = pm ? t : 0.f;
         }
         const float bn = (xq[q] - mu) * a + be;
@@ -354,7 +354,7 @@ __global__ __launch_bounds__(512, 1) void k_sp_bwd_fused(SpBwdParams P) {
         }
         if (P.write_dx && live) dst[pos] = d;
         if (pos < G::NPOS) {
-          const float fx = live ? (P.relu ? fmaxf(bn, 0.f) : bn) : 0.f;
+          const float fx = live ? (P.relu ? relu_max(bn) : bn) : 0.f;
           __bf16 *xr = xbi + pos * (G::XBP / 2);  // row (frame, w) = pos
           xr[0] = (__bf16)fx;
         }
@@ -764,7 +764,7 @@ __global__ __launch_bounds__(512, 1) void k_sp50_dx(Sp50Params P) {
       if (pv) {
         const float t = bn_pre(xv, pmu, pa, pb);
         uh = bn_hat(xv, pmu, pis);
-        pm = t > 0.f;
+        pm = relu_on(t);
         xv = pm ? t : 0.f;
       }
       const float bn = bn_pre(xv, mu, ga, be);
@@ -941,7 +941,7 @@ __global__ __launch_bounds__(512, 1) void k_sp50_dA(Sp50Params P) {
           float xv = xr[q];
           if (pv) xv = bn_relu(bn_pre(xv, pmu, pa, pb));
           const float bn = bn_pre(xv, mu, ga, be);
-          const float fx = pos < live ? (P.relu ? fmaxf(bn, 0.f) : bn) : 0.f;
+          const float fx = pos < live ? (P.relu ? relu_max(bn) : bn) : 0.f;
           xbi[pos * (G::XBP / 2)] = (__bf16)fx;
         }
       }

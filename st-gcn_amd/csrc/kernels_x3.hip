@@ -375,7 +375,7 @@ __device__ __forceinline__ void spb_epilogue(const ConvGemmParams &p, floatx16 (
             if (pv) {
               const float t = pbn.pre(xx);
               uh = pbn.hat(xx);
-              pm = t > 0.f;
+              pm = relu_on(t);
               xx = pm ? t : 0.f;
             }
             const float bn = bn1.pre(xx);

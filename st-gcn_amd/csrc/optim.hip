@@ -144,7 +144,8 @@ __global__ __launch_bounds__(256) void k_adam(const T *tab, const int64_t *chunk
     v = v + (s.one_minus_beta2 * g) * g;
     float vd = v;
     if constexpr (AMS) {
-      vd = fmaxf(t.vmax[e], v);
+      const float vm = t.vmax[e];
+      vd = (v > vm || v != v) ? v : vm;  // torch.maximum: a NaN on either side stays
       t.vmax[e] = vd;
     }
     const float denom = sqrtf(vd) / s.bc2_sqrt + s.eps;
@@ -262,7 +263,8 @@ __global__ __launch_bounds__(256) void k_grad_norm(const double *partials, int64
   if (threadIdx.x == 0) {
     const float norm = (float)sqrt(s);
     *norm_out = norm;
-    *coef_out = fminf(1.f, max_norm / (norm + 1e-6f));
+    const float c = max_norm / (norm + 1e-6f);
+    *coef_out = c > 1.f ? 1.f : c;  // clamp(max = 1): a NaN norm gives a NaN coefficient
   }
 }
 

@@ -12,6 +12,7 @@ import torch.multiprocessing as mp
 import torch.nn as nn
 
 from conftest import ROOT, load_npz
+from gates import worst_of
 
 
 def _free_port():
@@ -76,10 +77,11 @@ def _worker(rank, world, port, out_q, T, bucket_bytes):
         # expected: mean over shards of per-shard grads (computed locally)
         per = [_shard_grads(params, buffers, xs[r], ys[r]) for r in range(world)]
         want = [sum(g[i] for g in per) / world for i in range(len(got))]
-        worst = 0.0
+        errs = []
         for a, b in zip(got, want):
             denom = max(b.abs().max().item(), 1e-12)
-            worst = max(worst, (a - b).abs().max().item() / denom)
+            errs.append((a - b).abs().max().item() / denom)
+        worst = worst_of(errs)  # (NaN when a gradient holds one: tests/gates.py)
         # every rank ends with identical grads
         flat = torch.cat([g.reshape(-1) for g in got])
         ref = flat.clone()
@@ -145,7 +147,8 @@ def _accum_worker(rank, world, port, out_q):
             model(xs[step, rank]).square().sum().backward()
             dp.synchronize()
             want = mean_over_ranks(step)
-            errs.append(max((p.grad - w).abs().max().item() for p, w in zip(model.parameters(), want)))
+            errs.append(worst_of((p.grad - w).abs().max().item()
+                                 for p, w in zip(model.parameters(), want)))
         # accumulation: micro-batch 0 under no_sync, micro-batch 1 reduces the sum
         dp.zero_grad()
         with dp.no_sync():
@@ -153,7 +156,8 @@ def _accum_worker(rank, world, port, out_q):
         model(xs[1, rank]).square().sum().backward()
         dp.synchronize()
         want = mean_over_ranks(0, 1)
-        errs.append(max((p.grad - w).abs().max().item() for p, w in zip(model.parameters(), want)))
+        errs.append(worst_of((p.grad - w).abs().max().item()
+                                 for p, w in zip(model.parameters(), want)))
         # a second backward before synchronize() raises before accumulating
         dp.zero_grad()
         model(xs[2, rank]).square().sum().backward()
@@ -164,7 +168,8 @@ def _accum_worker(rank, world, port, out_q):
             raised = "no_sync" in str(e)
         dp.synchronize()
         want = mean_over_ranks(2)
-        errs.append(max((p.grad - w).abs().max().item() for p, w in zip(model.parameters(), want)))
+        errs.append(worst_of((p.grad - w).abs().max().item()
+                                 for p, w in zip(model.parameters(), want)))
         # a synced backward (all-reduces in flight), then a
         # no_sync() backward before synchronize() -- it would add into buffers
         # that are being reduced, so it raises too
@@ -178,8 +183,9 @@ def _accum_worker(rank, world, port, out_q):
             raised2 = "no_sync" in str(e)
         dp.synchronize()
         want = mean_over_ranks(0)
-        errs.append(max((p.grad - w).abs().max().item() for p, w in zip(model.parameters(), want)))
-        out_q.put((rank, max(errs), raised and raised2))
+        errs.append(worst_of((p.grad - w).abs().max().item()
+                                 for p, w in zip(model.parameters(), want)))
+        out_q.put((rank, worst_of(errs), raised and raised2))
     finally:
         dist.destroy_process_group()
 
@@ -243,9 +249,9 @@ def _unused_worker(rank, world, port, out_q):
             ref = _WithUnused()
             ref(x[r]).square().sum().backward()
             want.append([ref.a.grad, ref.b.grad])
-        err = max((model.a.grad - (want[0][0] + want[1][0]) / world).abs().max().item(),
-                  (model.b.grad - (want[0][1] + want[1][1]) / world).abs().max().item(),
-                  model.unused.grad.abs().max().item())
+        err = worst_of([(model.a.grad - (want[0][0] + want[1][0]) / world).abs().max().item(),
+                        (model.b.grad - (want[0][1] + want[1][1]) / world).abs().max().item(),
+                        model.unused.grad.abs().max().item()])
         out_q.put((rank, err, raised))
     finally:
         dist.destroy_process_group()

@@ -17,6 +17,7 @@ import pytest
 import torch
 
 from conftest import block_fixtures, load_npz, rel_to_max
+from gates import exceeds
 from oracle import ref_cpu
 
 pytestmark = pytest.mark.gpu
@@ -109,12 +110,12 @@ def _compare(got, want, residual=False, tol=TOL, floor=None):
         if k == "grad.temporalConv.bias" and not residual:
             err = float(np.abs(gv - wv).max())
             lim = max(ATOL_ZERO, 2.0 * floor.get("abs:" + k, 0.0)) if floor else ATOL_ZERO
-            if err > lim:
+            if exceeds(err, lim):
                 bad.append((k, err, lim))
             continue
         err = rel_to_max(gv, wv)
         lim = max(tol, 2.0 * floor.get(k, 0.0)) if floor else tol
-        if err > lim:
+        if exceeds(err, lim):
             bad.append((k, err, lim))
     assert not bad, "; ".join(f"{k}: {e:.2e} > {l:.1e}" for k, e, l in bad)
 

@@ -25,6 +25,7 @@ import pytest
 import torch
 
 from conftest import GOLDEN, load_npz, rel_to_max
+from gates import exceeds
 from oracle import ref_cpu
 from test_gpu_block import DEV, TOL, _random_case, _to_dev
 from test_gpu_stack import capture_relu_masks, check_relu_ties, gate_stack_grads, \
@@ -201,10 +202,11 @@ def test_block_eval_mode_backward(pkg, case, residual, gemm):
     _check_eval_backward(pkg, case, residual, gemm)
 
 
-def _check_eval_backward(pkg, case, residual, gemm, to_dev=_to_dev):
-    """to_dev: (tensor, name) -> GPU tensor (test_gpu_block._to_dev); another hook
-    also re-places the module's parameters and buffers."""
-    arrays, x, g = _eval_case(pkg, case, residual)
+def _run_eval_backward(pkg, arrays, x, g, case, residual, gemm, to_dev=_to_dev):
+    """The module's block in eval mode, forward and backward on the GPU:
+    (block, y, result dict, params, buffers). to_dev: (tensor, name) -> GPU
+    tensor (test_gpu_block._to_dev); another hook also re-places the module's
+    parameters and buffers."""
     p, b = ref_cpu.block_params_from_arrays(arrays, dtype=torch.float32, requires_grad=False)
     stride = case[2]
     C_in, C_out = case[0], case[1]
@@ -226,6 +228,16 @@ def _check_eval_backward(pkg, case, residual, gemm, to_dev=_to_dev):
     y = blk(xd)
     y.backward(to_dev(g, "g"))
     torch.cuda.synchronize()
+    got = {"y": y.detach().cpu(), "grad.x": xd.grad.cpu()}
+    got.update({"grad." + k: v.grad.cpu() for k, v in blk.named_parameters()})
+    return blk, y, got, p, b
+
+
+def _check_eval_backward(pkg, case, residual, gemm, to_dev=_to_dev):
+    """to_dev: as in ``_run_eval_backward``."""
+    arrays, x, g = _eval_case(pkg, case, residual)
+    blk, y, got, p, b = _run_eval_backward(pkg, arrays, x, g, case, residual, gemm, to_dev)
+    stride = case[2]
 
     def oracle(dtype, gemm_bf16=False):
         pp = {k: v.to(dtype).requires_grad_(True) for k, v in p.items()}
@@ -240,8 +252,6 @@ def _check_eval_backward(pkg, case, residual, gemm, to_dev=_to_dev):
         return out
 
     want = oracle(torch.float64)
-    got = {"y": y.detach().cpu(), "grad.x": xd.grad.cpu()}
-    got.update({"grad." + k: v.grad.cpu() for k, v in blk.named_parameters()})
     if gemm == "bf16":  # SURVEY §8c bf16 gate, or 3x the reference's own bf16-operand error
         ref16 = oracle(torch.float32, gemm_bf16=True)
         gate = {k: max(2e-2, 3 * rel_to_max(ref16[k].double().numpy(), w.double().numpy()))
@@ -323,15 +333,21 @@ def test_legacy_stgcn_eval_matches_reference(pkg):
     p32, _, _, _ = _legacy_oracle(ref, torch.float32)
     gate_stack_grads(model, {k: v.grad for k, v in p64.items()},
                      {k: v.grad for k, v in p32.items()}, skip=())
+    _gate_sampled_grads(model.named_parameters(), ref)
+
+
+def _gate_sampled_grads(named_parameters, ref):
+    """Gradients at the reference's sampled indices (pidx.<name>) against its
+    recorded values (gval.<name>): 1e-4, dA 1e-3."""
     bad = []
-    for k, v in model.named_parameters():
+    for k, v in named_parameters:
         if k.startswith("Masks."):
             assert v.grad is None
             continue
         idx = torch.as_tensor(ref["pidx." + k])
         got = v.grad.detach().cpu().reshape(-1)[idx].numpy()
         err = rel_to_max(got, ref["gval." + k])
-        if err > (1e-3 if k.endswith("spatialConv.A") else 1e-4):
+        if exceeds(err, 1e-3 if k.endswith("spatialConv.A") else 1e-4):
             bad.append(f"{k}: sampled {err:.2e}")
     assert not bad, "; ".join(bad)
 
@@ -366,8 +382,13 @@ def test_chain_with_tiny_bn2_gamma(pkg, gval):
     torch.nn.functional.cross_entropy(out1, lab).backward()
     torch.nn.functional.cross_entropy(out2, lab).backward()
     torch.cuda.synchronize()
+    _gate_chain_pairs(m1.named_parameters(), m2.named_parameters())
+
+
+def _gate_chain_pairs(named1, named2):
+    """Gradients of the chained stack (named1) against the unchained one's."""
     bad = []
-    for (k, a), (_, b) in zip(m1.named_parameters(), m2.named_parameters()):
+    for (k, a), (_, b) in zip(named1, named2):
         ga, gb = a.grad.detach().cpu().double().numpy(), b.grad.detach().cpu().double().numpy()
         assert np.isfinite(ga).all(), k
         if np.abs(gb).max() == 0 or k.endswith("temporalConv.bias"):  # (analytically 0)
@@ -376,6 +397,6 @@ def test_chain_with_tiny_bn2_gamma(pkg, gval):
         # the whole batch (the chain sums them in a different kernel and order)
         tol = 2e-3 if k.endswith("spatialConv.A") else 5e-4 if ".batch_n" in k else 1e-4
         err = rel_to_max(ga, gb)
-        if err > tol:
+        if exceeds(err, tol):
             bad.append(f"{k}: {err:.2e} > {tol:.0e}")
     assert not bad, "; ".join(bad)

@@ -15,6 +15,7 @@ import pytest
 import torch
 
 from conftest import load_npz, rel_to_max
+from gates import exceeds
 from oracle import ref_cpu
 
 pytestmark = pytest.mark.gpu
@@ -73,7 +74,7 @@ def gate_stack_grads(model, g64, g32, skip=("temporalConv.bias",)):
         want = g64[k].detach().double().numpy()
         floor = rel_to_max(g32[k].detach().double().numpy(), want)
         err = rel_to_max(v.grad.detach().cpu().double().numpy(), want)
-        if err > max(1e-4, 3 * floor):
+        if exceeds(err, max(1e-4, 3 * floor)):
             bad.append(f"{k}: {err:.2e} (ref32 {floor:.2e})")
     assert not bad, "; ".join(bad)
 
@@ -124,7 +125,7 @@ def gate_chained_vs_oracle(model, p0, b0, x_nctv, lab, masks, gemm, residual=Fal
         want = g64[k].detach().double().numpy()
         floor = rel_to_max(gref[k].detach().double().numpy(), want)
         err = rel_to_max(v.grad.detach().cpu().double().numpy(), want)
-        if err > max(lim, fac * floor):
+        if exceeds(err, max(lim, fac * floor)):
             bad.append(f"{k}: {err:.2e} (ref {floor:.2e})")
     assert not bad, "; ".join(bad)
 
@@ -161,7 +162,7 @@ def test_stack_cfg1_matches_reference(pkg):
         want = g64[k].detach().double()
         floor = rel_to_max(g32[k].detach().double().numpy(), want.numpy())
         err = rel_to_max(got.numpy(), want.numpy())
-        if err > max(1e-4, 3 * floor):
+        if exceeds(err, max(1e-4, 3 * floor)):
             bad.append(f"{k}: {err:.2e} (ref32 {floor:.2e})")
     assert not bad, "; ".join(bad)
     # running statistics after one training step
@@ -229,7 +230,7 @@ def test_stack_chain_small_bn2_gamma(pkg, residual, gemm):
             continue
         tol = 2e-3 if k.endswith("spatialConv.A") else 1e-4
         err = rel_to_max(ga, gb)
-        if err > tol:
+        if exceeds(err, tol):
             bad.append(f"{k}: {err:.2e} > {tol:.0e}")
     assert not bad, "; ".join(bad)
 
@@ -281,7 +282,7 @@ def test_stack_chain_matches_unchained(pkg, residual, drop):
             continue
         tol = 2e-3 if k.endswith("spatialConv.A") else 1e-4
         err = rel_to_max(ga, gb)
-        if err > tol:
+        if exceeds(err, tol):
             bad.append(f"{k}: {err:.2e} > {tol:.0e}")
     assert not bad, "; ".join(bad)
     for (k, a), (_, b) in zip(m1.named_buffers(), m2.named_buffers()):
@@ -484,7 +485,7 @@ def test_stack_bf16_cfg3_shape(pkg):
         floor = rel_to_max(g16[k].detach().double().numpy(), want.numpy())
         err = rel_to_max(got.numpy(), want.numpy())
         worst = max(worst, err)
-        if err > max(2e-2, 4 * floor):
+        if exceeds(err, max(2e-2, 4 * floor)):
             bad.append(f"{k}: {err:.2e} (ref bf16 {floor:.2e})")
     print("logits", lerr, "worst grad", worst)
     assert not bad, "; ".join(bad)
@@ -579,7 +580,7 @@ def test_stack_chain_matches_unchained_bf16x3(pkg, residual, f32_gemm):
             err = np.abs(ga - gb).max() / scale
         else:
             err = rel_to_max(ga, gb)
-        if err > tol:
+        if exceeds(err, tol):
             bad.append(f"{k}: {err:.2e} > {tol:.0e}")
     assert not bad, "; ".join(bad)
 
@@ -663,7 +664,8 @@ def test_stack_bf16_multi_seed(pkg, V):
         e = np.array([r[0][k] for r in runs])
         f = np.array([r[1][k] for r in runs])
         ratios[k] = e.mean() / max(f.mean(), 1e-30)
-        if e.mean() > max(2e-2, 2.5 * f.mean()) or e.max() > max(2e-2, 4 * f.max()):
+        if exceeds(e.mean(), max(2e-2, 2.5 * f.mean())) or \
+                exceeds(e.max(), max(2e-2, 4 * f.max())):
             bad.append(f"{k}: mean {e.mean():.2e} max {e.max():.2e} "
                        f"(ref bf16 mean {f.mean():.2e} max {f.max():.2e})")
     worst = sorted(ratios.items(), key=lambda kv: -kv[1])[:5]
